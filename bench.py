@@ -13,10 +13,14 @@ per step -- total work fixed, "strong" scaling.  The same line carries, as the n
 measurement (--parallel dp): every rank trains on its OWN 100-image batch -- global batch 100 N, gradients averaged,
 each rank scores the queries of all ranks against its exemplar shard and the partials return to their owners ("weak").
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0 (metric, value, unit, higher_is_better, dtype, ms_per_step = wall time of the --steps timed
+steps / --steps).  A plain run sets up, warms up, times the steps and prints; --full adds what takes runs of its own:
   roofline     -- the dominant kernel (the fp32-MFMA GEMM behind GatedDense), algorithmic flops per
-                  launch / mean launch duration measured with HIP events inside the timed region
+                  launch / mean launch duration measured with HIP events on eager probe steps after the timed region,
+                  and inside the replayed graph from a child run under rocprofv3
   cpu_baseline -- the numpy oracle's train step (oracle/evae_oracle.py) timed on the host cores
+  test_log_px, amdahl_ceiling, dp -- the IWAE evaluator, a child run at 200 exemplars, the data-parallel leg of --gpus N
+--dump-outputs DIR writes the last timed step's (loss, -RE, KL) and the updated parameters as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -41,6 +45,10 @@ MLP_CONFIGS = {"c1": ("vae", 1000, 50000), "c2": ("vae", 25000, 50000), "c4": ("
                # c2 with the kNN-approximate prior (reference models/BaseModel.py:256-271): 25 000 candidates per step, top-10 of
                # every batch row among their cached latents, the B * k = 1000 slots re-encoded
                "c2a": ("vae", 25000, 50000)}
+# untimed 10-step windows of replays in front of the timed region: a fixed count (the most the earlier stop-when-two-windows-agree
+# rule ever took), so that the steps in front of the last timed one -- and with them its outputs -- do not depend on timing
+RAMP_WINDOWS = 4
+DUMP_BYTES = 64 << 20                 # --dump-outputs: the most it writes in all
 
 
 def parse():
@@ -66,7 +74,7 @@ def parse():
     ap.add_argument("--no-graph-profile", action="store_true",
                     help="headline line only: do not run the child process under rocprofv3 that times the kernels INSIDE the replayed graph")
     ap.add_argument("--no-ramp", action="store_true",
-                    help="skip the untimed clock-ramp replays in front of the timed region (10-step windows until two agree to 2 %%)")
+                    help="skip the untimed clock-ramp replays in front of the timed region (%d 10-step windows)" % RAMP_WINDOWS)
     ap.add_argument("--probe-warmup", type=int, default=20,
                     help="untimed eager steps in front of the probe steps (clock ramp after the host pause)")
     ap.add_argument("--probe-steps", type=int, default=20,
@@ -75,6 +83,13 @@ def parse():
                     help="test images for the IWAE test log p(x) leg (S=5000 samples each vs all 50 000 exemplars); 0 disables")
     ap.add_argument("--cpu-baseline-steps", type=int, default=80,
                     help="oracle steps timed for cpu_baseline (0 disables)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: the roofline objects (eager probe steps, the child run "
+                         "under rocprofv3), the CPU baselines, the IWAE leg, the amdahl_ceiling child and the nested dp measurement of "
+                         "--gpus N.  Off: set up, warm up, time --steps steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB in all); same arguments, same inputs, run to run")
     return ap.parse_args()
 
 
@@ -335,6 +350,80 @@ def line(metric, value, unit, a, dt, workload, roof, extra=None, world=1, launch
     return out
 
 
+def dump_outputs(d, arrays):
+    """--dump-outputs: one d/<name>.npy per array, float64 for float64 and integer arrays, float32 otherwise.  When the files
+    would together exceed DUMP_BYTES, every array over an equal share of it is replaced by a fixed sample of its flattened elements
+    (positions drawn without replacement by numpy's RandomState(0), ascending), so two runs write the same elements."""
+    os.makedirs(d, exist_ok=True)
+    out = {}
+    for name, v in arrays.items():
+        v = v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+        out[name] = v.astype(np.float64 if (v.dtype == np.float64 or v.dtype.kind in "iub") else np.float32)
+    room = DUMP_BYTES - 256 * len(out)          # (each file's .npy header)
+    if sum(v.nbytes for v in out.values()) > room:
+        share = room // len(out)
+        for name, v in out.items():
+            if v.nbytes > share:
+                k = share // v.itemsize
+                out[name] = v.reshape(-1)[np.sort(np.random.RandomState(0).choice(v.size, k, replace=False))]
+    for name, v in out.items():
+        np.save(os.path.join(d, name + ".npy"), v)
+
+
+def step_arrays(model, out3):
+    """What a training step hands its caller: (loss, -RE, KL) of the step (GraphedTrainStep's return value) and the parameters
+    after the optimizer's update."""
+    arr = {} if out3 is None else {"loss_negre_kl": out3}
+    arr.update(("param." + n, p) for n, p in model.named_parameters())
+    return arr
+
+
+def conv_roofline(a, c5, runner, n_ex):
+    """--full, c3 / c5: the dominant kernel, timed with HIP events at the shape it has in the step."""
+    from evae import ops
+    with torch.no_grad():
+        if c5:
+            # a residual block of the decoder (96 channels, 32 x 32, the batch's 100 images) as the step launches it: the window
+            # kernel over pixel images with bias + residual + the next block's ELU image in the epilogue (csrc/evae_conv_win.h)
+            nimg, ci, co, k_, hw = B, 96, 96, 3, 32
+            pr = ops.res_window_probe(nimg, ci, hw, k_)
+            us = time_launches(pr["fwd"], reps=4)
+            us_d = time_launches(pr["dgrad"], reps=4)
+            us_w = time_launches(pr["wgrad"], reps=4)
+            del pr
+            flops = 2.0 * nimg * hw * hw * ci * k_ * k_ * co
+            kern = ("residual block 96 -> 96, 3x3, 32 x 32, %d images on pixel images (evae_cw_res_fwd: conv_win_kernel<3, 4, 2, 576>, "
+                    "bias + residual + ELU image in the epilogue)" % nimg)
+        else:
+            # the gated 5 x 5 layer of q_z_layers over the exemplar images the step encodes, as the stack launches it: the window
+            # kernel over pre-split pixel images (csrc/evae_conv_win.h)
+            dd0 = getattr(runner, "dedup", None) if runner is not None else None
+            nimg, ci, co, k_, hw = (dd0["cap"] if dd0 else n_ex), 32, 64, 5, 14
+            pr = ops.conv_window_probe(nimg, ci, hw, co, k_, 1, out_planar=True)
+            us = time_launches(pr["fwd"], reps=2)
+            us_d = time_launches(pr["dgrad"], reps=2)
+            us_w = time_launches(pr["wgrad"], reps=2)
+            del pr
+            flops = 2.0 * nimg * hw * hw * ci * k_ * k_ * 2 * co
+            kern = ("gated conv 32 -> 64, 5x5, 14 x 14, %d images on pixel images (evae_cw_fwd_gated: conv_win_kernel<0, 2, 2, 320>, input "
+                    "window resident in LDS, gate + output image in the epilogue)" % nimg)
+    traffic, tsrc = pmc_traffic("res96_fwd" if c5 else "cw5_fwd", expect="conv_win_kernel<3, 4, 2, 576>" if c5 else "conv_win_kernel<0, 2, 2, 320>")
+    roof = mfma_roofline(kern, flops, 6.0 * flops, "bf16-mfma", us, traffic, tsrc)
+    if c5:
+        roof["kernels"] = [
+            {"launch": "its data gradient dx = dy + ELU'(x) conv_transpose(dy, w) (evae_cw_res_bwd_data: conv_win_kernel<4, 4, 2, 576>)",
+             "us": round(us_d, 1), "frac": round(flops / us_d / 1e6 / PEAK_BF16_MFMA_TFLOPS, 4)},
+            {"launch": "its weight gradient over pixel images (evae_cw_bwd_weight_plain: conv_wgrad_win_kernel<9, 224, 8, 2, false> x 3 channel-group pairs + finish)",
+             "us": round(us_w, 1), "frac": round(flops / us_w / 1e6 / PEAK_BF16_MFMA_TFLOPS, 4)}]
+    else:
+        roof["kernels"] = [
+            {"launch": "data gradient + gate derivative of the layer below (evae_cw_bwd_data_gate: conv_win_kernel<1, 4, 1, 576>)",
+             "us": round(us_d, 1), "frac": round(flops / us_d / 1e6 / PEAK_BF16_MFMA_TFLOPS, 4)},
+            {"launch": "weight gradient over pixel images (evae_cw_bwd_weight: conv_wgrad_win_kernel<13 | 12, 192, 8, 1, false> + finish)",
+             "us": round(us_w, 1), "frac": round(flops / us_w / 1e6 / PEAK_BF16_MFMA_TFLOPS, 4)}]
+    return roof
+
+
 def other_config(a, dev, rank, world, rccl_ranks=1, backend=None):
     """c3 / c5 (the convolutional configurations), iwae (the test log p(x) evaluator), topk (cache + top-K): the same JSON
     line as the headline, each with the roofline object of ITS dominant kernel.  Single GPU."""
@@ -381,66 +470,34 @@ def other_config(a, dev, rank, world, rccl_ranks=1, backend=None):
         if runner is not None and cache is not None:
             cache = runner.set_cache(cache)       # static buffers: the captured launches read and refresh them in place
 
+        last = [None]                            # the eager step's (loss, RE, KL): --dump-outputs
+
         def step(i):
             s_ = (i * B) % (n_train - B)
             if runner is not None:
                 return runner(data_dev[s_:s_ + B], idx_all[s_:s_ + B], 0.5)
             opt.zero_grad()
-            loss, _, _ = model.calculate_loss((data_dev[s_:s_ + B], idx_all[s_:s_ + B]), 0.5, average=True, cache=cache,
-                                              dataset=dataset)
+            loss, RE, KL = model.calculate_loss((data_dev[s_:s_ + B], idx_all[s_:s_ + B]), 0.5, average=True, cache=cache,
+                                                dataset=dataset)
             loss.backward()
             opt.step()
+            last[0] = (loss, RE, KL)
         for i in range(a.warmup):
             step(i)
         torch.cuda.synchronize()
+        out3 = None
         t0 = time.perf_counter()
         for i in range(a.steps):
-            step(a.warmup + i)
+            out3 = step(a.warmup + i)
         t_issue = time.perf_counter() - t0       # the host has issued every launch (eager legs: is the step host-bound?)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
-        # the dominant kernel, timed with HIP events at the shape it has in the step
-        with torch.no_grad():
-            if c5:
-                # a residual block of the decoder (96 channels, 32 x 32, the batch's 100 images) as the step launches it: the window
-                # kernel over pixel images with bias + residual + the next block's ELU image in the epilogue (csrc/evae_conv_win.h)
-                nimg, ci, co, k_, hw = B, 96, 96, 3, 32
-                pr = ops.res_window_probe(nimg, ci, hw, k_)
-                us = time_launches(pr["fwd"], reps=4)
-                us_d = time_launches(pr["dgrad"], reps=4)
-                us_w = time_launches(pr["wgrad"], reps=4)
-                del pr
-                flops = 2.0 * nimg * hw * hw * ci * k_ * k_ * co
-                kern = ("residual block 96 -> 96, 3x3, 32 x 32, %d images on pixel images (evae_cw_res_fwd: conv_win_kernel<3, 4, 2, 576>, "
-                        "bias + residual + ELU image in the epilogue)" % nimg)
-            else:
-                # the gated 5 x 5 layer of q_z_layers over the exemplar images the step encodes, as the stack launches it: the window
-                # kernel over pre-split pixel images (csrc/evae_conv_win.h)
-                dd0 = getattr(runner, "dedup", None) if runner is not None else None
-                nimg, ci, co, k_, hw = (dd0["cap"] if dd0 else n_ex), 32, 64, 5, 14
-                pr = ops.conv_window_probe(nimg, ci, hw, co, k_, 1, out_planar=True)
-                us = time_launches(pr["fwd"], reps=2)
-                us_d = time_launches(pr["dgrad"], reps=2)
-                us_w = time_launches(pr["wgrad"], reps=2)
-                del pr
-                flops = 2.0 * nimg * hw * hw * ci * k_ * k_ * 2 * co
-                kern = ("gated conv 32 -> 64, 5x5, 14 x 14, %d images on pixel images (evae_cw_fwd_gated: conv_win_kernel<0, 2, 2, 320>, input "
-                        "window resident in LDS, gate + output image in the epilogue)" % nimg)
-        traffic, tsrc = pmc_traffic("res96_fwd" if c5 else "cw5_fwd", expect="conv_win_kernel<3, 4, 2, 576>" if c5 else "conv_win_kernel<0, 2, 2, 320>")
-        if c5:
-            roof = mfma_roofline(kern, flops, 6.0 * flops, "bf16-mfma", us, traffic, tsrc)
-            roof["kernels"] = [
-                {"launch": "its data gradient dx = dy + ELU'(x) conv_transpose(dy, w) (evae_cw_res_bwd_data: conv_win_kernel<4, 4, 2, 576>)",
-                 "us": round(us_d, 1), "frac": round(flops / us_d / 1e6 / PEAK_BF16_MFMA_TFLOPS, 4)},
-                {"launch": "its weight gradient over pixel images (evae_cw_bwd_weight_plain: conv_wgrad_win_kernel<9, 224, 8, 2, false> x 3 channel-group pairs + finish)",
-                 "us": round(us_w, 1), "frac": round(flops / us_w / 1e6 / PEAK_BF16_MFMA_TFLOPS, 4)}]
-        else:
-            roof = mfma_roofline(kern, flops, 6.0 * flops, "bf16-mfma", us, traffic, tsrc)
-            roof["kernels"] = [
-                {"launch": "data gradient + gate derivative of the layer below (evae_cw_bwd_data_gate: conv_win_kernel<1, 4, 1, 576>)",
-                 "us": round(us_d, 1), "frac": round(flops / us_d / 1e6 / PEAK_BF16_MFMA_TFLOPS, 4)},
-                {"launch": "weight gradient over pixel images (evae_cw_bwd_weight: conv_wgrad_win_kernel<13 | 12, 192, 8, 1, false> + finish)",
-                 "us": round(us_w, 1), "frac": round(flops / us_w / 1e6 / PEAK_BF16_MFMA_TFLOPS, 4)}]
+        if a.dump_outputs:
+            if out3 is None and last[0] is not None:
+                loss, RE, KL = (t_.detach().reshape(()) for t_ in last[0])
+                out3 = torch.stack((loss, -RE, KL))
+            dump_outputs(a.dump_outputs, step_arrays(model, out3))
+        roof = conv_roofline(a, c5, runner, n_ex) if a.full else None
         wl = ("single_conv (fully_conv) + exemplar_prior, 3x64x64 continuous, z=256, approximate prior: top-10 over %d cached "
               "latents, <= 1000 exemplars re-encoded per step, batch %d (BASELINE.json configs[4], one GPU)" % (n_ex, B)) if c5 else \
              ("convhvae_2level + exemplar_prior, fashion_mnist-shaped binary 28x28, N=%d, batch %d, %d exemplars, exact prior "
@@ -493,27 +550,33 @@ def other_config(a, dev, rank, world, rccl_ranks=1, backend=None):
                 tt = torch.tensor([dt], device=dev, dtype=torch.float64)
                 dist.all_reduce(tt, op=dist.ReduceOp.MAX)
                 dt = float(tt.item())
-            # dominant kernel: the prior's forward for one evaluator pass (4 images x S samples against all N exemplars)
-            zq = cz[:1] + 0.3 * torch.randn(4 * args.S, Z, device=dev)
-            lv = clv[0].contiguous()
-            us = time_launches(lambda: ops.prior_lse_fwd(zq, cz, lv), reps=2)
+            if rank == 0 and a.dump_outputs:
+                dump_outputs(a.dump_outputs, {"neg_log_px": np.array([float(ll)], dtype=np.float64)})
+            if a.full:
+                # dominant kernel: the prior's forward for one evaluator pass (4 images x S samples against all N exemplars)
+                zq = cz[:1] + 0.3 * torch.randn(4 * args.S, Z, device=dev)
+                lv = clv[0].contiguous()
+                us = time_launches(lambda: ops.prior_lse_fwd(zq, cz, lv), reps=2)
         n_loc = int(cz.shape[0])                     # this rank's rows of the cache
-        flops = 2.0 * 4 * args.S * n_loc * Z
-        traffic, tsrc = pmc_traffic("prior_iwae")
-        executed, pipe = ops.gemm_pipe(n_loc, 4 * args.S, False, flops)      # streaming split-bf16 kernel when the pipe is on
-        kname = ("evae::prior_x6_lse_kernel<3> (+ staging pass and split merge; csrc/evae_prior_gemm.hip)" if pipe == "bf16-mfma"
-                 else "evae::prior_fwd_mfma_kernel<5, 4> (+ the split merge)")
-        roof = mfma_roofline(kname + ": 4 x %d importance samples x %d exemplars x z=%d, distance on the matrix cores, online "
-                                     "log-sum-exp" % (args.S, n_loc, Z), flops, executed, pipe, us, traffic if world == 1 else None, tsrc if world == 1 else None)
+        roof = None
+        if a.full:
+            flops = 2.0 * 4 * args.S * n_loc * Z
+            traffic, tsrc = pmc_traffic("prior_iwae")
+            executed, pipe = ops.gemm_pipe(n_loc, 4 * args.S, False, flops)      # streaming split-bf16 kernel when the pipe is on
+            kname = ("evae::prior_x6_lse_kernel<3> (+ staging pass and split merge; csrc/evae_prior_gemm.hip)" if pipe == "bf16-mfma"
+                     else "evae::prior_fwd_mfma_kernel<5, 4> (+ the split merge)")
+            roof = mfma_roofline(kname + ": 4 x %d importance samples x %d exemplars x z=%d, distance on the matrix cores, online "
+                                         "log-sum-exp" % (args.S, n_loc, Z), flops, executed, pipe, us, traffic if world == 1 else None, tsrc if world == 1 else None)
         a.steps = n_pass * nimg
+        cpu_iwae = world == 1 and a.cpu_baseline_steps > 0 and a.full
         if rank == 0:
             print(json.dumps(line("IWAE test log p(x) images/sec", round(n_pass * nimg / dt, 2), "images/sec", a, dt,
                                   "utils.evaluation.calculate_likelihood: vae, S=%d importance samples per test image against all %d "
                                   "training exemplars (the test-log-p(x) half of BASELINE.json's metric), %d test images per pass"
                                   % (args.S, N_TRAIN, nimg), roof, world=world,
                                   extra={"neg_log_px": round(float(ll), 3), "rccl_ranks": rccl_ranks, "backend": backend,
-                                         "cpu_baseline": (cpu_baseline_iwae(4, args.S, N_TRAIN) if (world == 1 and a.cpu_baseline_steps > 0) else None),
-                                         "cpu_baseline_reason": None if (world == 1 and a.cpu_baseline_steps > 0) else "rank 0 at N = 1 only / --cpu-baseline-steps 0",
+                                         "cpu_baseline": cpu_baseline_iwae(4, args.S, N_TRAIN) if cpu_iwae else None,
+                                         "cpu_baseline_reason": None if cpu_iwae else "rank 0 at N = 1 only / --cpu-baseline-steps 0 / no --full",
                                          "parallelism": "single GPU" if world == 1 else
                                          "latent cache row-sharded x%d (%d rows on rank 0), same test images on every rank, one "
                                          "all-gather of packed partial log-sum-exps per call" % (world, n_loc),
@@ -523,13 +586,18 @@ def other_config(a, dev, rank, world, rccl_ranks=1, backend=None):
             dist.destroy_process_group()
         return
     # topk: models/BaseModel.py:263-264 (distance + topk over the candidate cache), utils/knn_on_latent.py:4-9
-    res = []
+    res, last = [], {}
     for tag, Bq, N, zd in (("c2", 100, 25000, 40), ("c5", 100, 100000, 256)):
+        if tag != "c5" and not a.full:       # the headline is config 5's size
+            continue
         z_np, c_np = gi.clustered_latents(3, Bq, N, zd)
         q = torch.from_numpy(z_np).to(dev); cache = torch.from_numpy(c_np).to(dev)
-        us = time_launches(lambda: ops.pairdist_topk(q, cache, 10, want_val=False), reps=2)      # k = 10 (approximate_k)
+        us = time_launches(lambda: last.__setitem__(tag, ops.pairdist_topk(q, cache, 10, want_val=False)), reps=2)      # k = 10 (approximate_k)
         res.append((tag, Bq, N, zd, us))
-    tag, Bq, N, zd, us = res[1]
+    tag, Bq, N, zd, us = res[-1]
+    if a.dump_outputs:
+        idx_ = last["c5"][0] if isinstance(last["c5"], (tuple, list)) else last["c5"]
+        dump_outputs(a.dump_outputs, {"topk_indices": idx_})
     kk = 10
     algo_bytes = lambda Bq_, N_, z_: 4.0 * (N_ * z_ + Bq_ * z_) + 8.0 * Bq_ * kk      # ONE pass over the cache
     bytes_ = algo_bytes(Bq, N, zd)
@@ -543,11 +611,11 @@ def other_config(a, dev, rank, world, rccl_ranks=1, backend=None):
                                    "GB/s": round(algo_bytes(r[1], r[2], r[3]) / r[4] / 1e3, 1),
                                    "frac": round(algo_bytes(r[1], r[2], r[3]) / r[4] / 1e3 / PEAK_HBM_GBS, 4)} for r in res}}
     a.steps = 1
-    cb = cpu_baseline_topk(q, cache, kk) if a.cpu_baseline_steps > 0 else None
+    cb = cpu_baseline_topk(q, cache, kk) if (a.cpu_baseline_steps > 0 and a.full) else None
     print(json.dumps(line("top-K cache scan", round(Bq / (us * 1e-6), 1), "queries/sec", a, us * 1e-6,
                           "evae_pairdist_topk: k=10 nearest cached latents per query, bit-exact indices (config 5 sizes; config 2 "
-                          "sizes in roofline.other_sizes)", roof,
-                          extra={"cpu_baseline": cb, "cpu_baseline_reason": None if cb else "--cpu-baseline-steps 0"})))
+                          "sizes in roofline.other_sizes with --full)", roof,
+                          extra={"cpu_baseline": cb, "cpu_baseline_reason": None if cb else "--cpu-baseline-steps 0 / no --full"})))
 
 
 def capture_probe():
@@ -694,13 +762,14 @@ def main():
         loss.backward()
         opt.step()
         loss_acc.add_(loss.detach())
+        state["last"] = (loss, RE, KL)
 
     from evae.graph import GraphedTrainStep
     graphed = None if a.no_graph else GraphedTrainStep(model, opt, dataset, B, True)
     if graphed is not None and cache is not None:
         cache = graphed.set_cache(cache)      # static buffers: the captured launches read and refresh them in place
 
-    state = {"graphed": graphed}
+    state = {"graphed": graphed, "last": None}
 
     def step(i):
         g = state["graphed"]
@@ -749,16 +818,16 @@ def main():
     for i in range(1, a.warmup):
         step(i)
     # Untimed, in front of the timed region (VERDICT r02 #3b): (1) the capture happens here whatever --warmup says (the runner
-    # needs its eager warm-up calls + the capturing call), (2) replays until two consecutive 10-step windows agree to 2 %
-    # (cap 0.5 s): the clocks take tens of milliseconds to come up after the host-side setup, and a 20-step timed region is
-    # 14 ms.  Every rank takes the same decisions (window times are max-reduced).
+    # needs its eager warm-up calls + the capturing call), (2) RAMP_WINDOWS 10-step windows of replays: the clocks take tens of
+    # milliseconds to come up after the host-side setup, and a 20-step timed region is 14 ms.  ramp_settled: the last two windows
+    # agreed to 2 % (window times are max-reduced over the ranks).
     n_pre = a.warmup
     g_ = state["graphed"]
     while g_ is not None and state["graphed"] is g_ and g_.graph is None and not g_.failed and n_pre < a.warmup + 8:
         step(n_pre); n_pre += 1
     fence()
-    ramp_replays, ramp_ms, prev = 0, 0.0, None
-    while not a.no_ramp and ramp_ms < 500.0:
+    ramp_replays, ramp_ms, prev, ramp_settled = 0, 0.0, None, None
+    for _ in range(0 if a.no_ramp else RAMP_WINDOWS):
         tw = time.perf_counter()
         for _ in range(10):
             step(n_pre); n_pre += 1
@@ -769,8 +838,8 @@ def main():
             dist.all_reduce(tws, op=dist.ReduceOp.MAX)
             w_ms = float(tws.item())
         ramp_replays += 10; ramp_ms += w_ms
-        if prev is not None and abs(w_ms - prev) <= 0.02 * max(w_ms, prev):
-            break
+        if prev is not None:
+            ramp_settled = abs(w_ms - prev) <= 0.02 * max(w_ms, prev)
         prev = w_ms
     fence()
     # one event behind every step of the timed region (no synchronisation: read back after the closing fence) so that a short
@@ -791,6 +860,15 @@ def main():
     ops.prior_train_check()          # the one-launch prior's co-residency guard: raises if any block of any step gave up (outside the timed region)
     n_done = n_pre + a.steps
     g_ = state["graphed"]
+    if rank == 0 and a.dump_outputs:             # before the probe steps below train the model on
+        if g_ is not None:
+            out3 = g_.out
+        elif state["last"] is not None:
+            loss, RE, KL = (t_.detach().reshape(()) for t_ in state["last"])
+            out3 = torch.stack((loss, -RE, KL))
+        else:
+            out3 = None
+        dump_outputs(a.dump_outputs, step_arrays(model, out3))
     loss_sum = float(loss_acc.item()) + (float(g_.totals[0].item()) if g_ is not None else 0.0)
     # Per-kernel timing of the dominant kernel: HIP-event pairs around every GatedDense forward launch.
     # Event pairs cannot be read back from inside a replayed graph, so the same steps are run eagerly right
@@ -808,10 +886,11 @@ def main():
             return eager_step(i)
         s_ = batch_start(i)
         graphed.step_eagerly(data_dev[s_:s_ + B], idx_host[s_:s_ + B], beta)
-    for i in range(a.probe_warmup if graphed is not None else 0):
+    probing = graphed is not None and a.full        # (the roofline object: --full only)
+    for i in range(a.probe_warmup if probing else 0):
         probe_step(n_done + i)
     ops.PROBE = {"records": [], "min_flops": 2e9 if n_ex >= 10000 and not approx else 2e8}
-    for i in range(a.probe_steps if graphed is not None else 0):
+    for i in range(a.probe_steps if probing else 0):
         probe_step(n_done + a.probe_warmup + i)
     fence()
     probe, ops.PROBE = ops.PROBE, None
@@ -873,7 +952,7 @@ def main():
     # ... and the same launches INSIDE the replayed graph: a child run under rocprofv3; the eager event pairs above
     # time a launch alone-ish (the host paces eager steps), inside the replay it shares the machine with the side stream's launches
     gstats, gsrc = (None, "not the headline configuration on one GPU") if not (headline and world == 1 and state["graphed"] is not None and rank == 0) \
-        else (None, "--no-graph-profile") if a.no_graph_profile else graph_kernel_stats()
+        else (None, "--no-graph-profile") if a.no_graph_profile else (None, "no --full") if not a.full else graph_kernel_stats()
     sym_of = {pre: sym for pre, _, sym in pmc_of}
     for k_ in kernels:
         k_["in_graph_avg_launch_us"] = None
@@ -938,7 +1017,7 @@ def main():
 
     # second half of BASELINE.json's metric: test log p(x) (IWAE, S = 5000, all N_train exemplars as the prior)
     iwae = None
-    if world == 1 and a.iwae_images > 0 and a.config == "c2":
+    if world == 1 and a.iwae_images > 0 and a.config == "c2" and a.full:
         from utils.evaluation import calculate_likelihood
         test = torch.from_numpy(gi.binary_images(2, a.iwae_images))
         test_ds = torch.utils.data.TensorDataset(test, torch.zeros(len(test)))
@@ -983,7 +1062,7 @@ def main():
         coll["issued_in_one_step"] = {"count": len(coll_seen), "list": coll_seen}     # counted, see above
     # second measurement of a multi-GPU run: the data-parallel mode, same process group, its own model / optimizer / runner
     dp_line = None
-    if world > 1 and not dp and not a.no_dp_line:
+    if world > 1 and not dp and not a.no_dp_line and a.full:
         try:
             from evae.graph import GraphedTrainStep as _G
             args2 = model_args("cuda:%d" % local_rank, n_ex, sharded=True, shard_batch=True, model_name=model_name, n_train=n_train)
@@ -1051,7 +1130,8 @@ def main():
                        "launch": "eager" if graphed is None else "hipGraph replay of the whole step"},
             "collectives": coll, "rccl_ranks": rccl_ranks, "backend": backend,
             "dp": dp_line,
-            "host_issue_ms_per_step": round(1e3 * t_issue / a.steps, 4), "ramp_replays": ramp_replays, "ramp_ms": round(ramp_ms, 2), "untimed_steps": n_pre,
+            "host_issue_ms_per_step": round(1e3 * t_issue / a.steps, 4), "ramp_replays": ramp_replays, "ramp_ms": round(ramp_ms, 2), "ramp_settled": ramp_settled,
+            "untimed_steps": n_pre,
             "step_ms": step_ms,
             **({"per_step_ms": [round(t_, 4) for t_ in per_step_raw]} if os.environ.get("EVAE_BENCH_DUMP_STEPS") == "1" else {}),
             "mean_loss": round(final_loss, 4), "mean_loss_f64": final_loss, "steps_in_mean_loss": n_done,
@@ -1070,14 +1150,15 @@ def main():
             "test_log_px": iwae,
             "cpu_baseline": None,
         }
-        if world == 1 and a.cpu_baseline_steps > 0 and model_name == "vae" and not approx:
+        if world == 1 and a.cpu_baseline_steps > 0 and model_name == "vae" and not approx and a.full:
             out["cpu_baseline"] = cpu_baseline(a.cpu_baseline_steps, n_ex, n_train)
         else:
             out["cpu_baseline_reason"] = ("rank 0 at N = 1 only" if world > 1 else "--cpu-baseline-steps 0" if a.cpu_baseline_steps <= 0 else
+                                          "no --full" if not a.full else
                                           (NO_PORT % "hvae_2level") if model_name != "vae" else
                                           "the oracle's training step restates the exact prior; the approximate (cache + top-k) step is held to "
                                           "golden G10 of the real reference")
-        if world == 1 and a.config == "c2" and a.exemplars is None and not a.no_amdahl:
+        if world == 1 and a.config == "c2" and a.exemplars is None and not a.no_amdahl and a.full:
             out["amdahl_ceiling"] = amdahl_ceiling(1e3 * dt / a.steps, n_ex)
         print(json.dumps(out))
     if world > 1:

@@ -330,3 +330,29 @@ def test_host_dedup_of_an_exemplar_draw():
             assert lib.evae_host_dedup(p(d), n, N, U - 1, p(rows), p(inv), p(rep), p(mult)) == -1
     bad = torch.tensor([0, 9], dtype=torch.int64)
     assert lib.evae_host_dedup(C.c_void_p(bad.data_ptr()), 2, 5, 4, p(rows), p(inv), p(rep), p(mult)) == -1
+
+
+def test_bench_dump_outputs_types_budget_and_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 / float64 files, at most DUMP_BYTES on disk in all, and the same fixed sample of an
+    over-budget array from run to run; --full and --dump-outputs parse, a plain run has neither."""
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", str(tmp_path / "x")])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == str(tmp_path / "x")
+    monkeypatch.setattr(bench, "DUMP_BYTES", 1 << 20)
+    small = {"i": torch.arange(5), "d": torch.ones(3, dtype=torch.float64), "h": torch.zeros(2, dtype=torch.float16)}
+    bench.dump_outputs(str(tmp_path / "s"), small)
+    assert {f: np.load(tmp_path / "s" / f).dtype for f in os.listdir(tmp_path / "s")} == \
+        {"i.npy": np.float64, "d.npy": np.float64, "h.npy": np.float32}
+    big = {"a": torch.randn(300000), "b": torch.randn(10)}
+    for d in ("b1", "b2"):
+        bench.dump_outputs(str(tmp_path / d), big)
+        assert sum(os.path.getsize(tmp_path / d / f) for f in os.listdir(tmp_path / d)) <= 1 << 20
+    a1, a2 = np.load(tmp_path / "b1" / "a.npy"), np.load(tmp_path / "b2" / "a.npy")
+    assert a1.size < 300000 and np.array_equal(a1, a2) and np.isin(a1, big["a"].numpy()).all()
+    assert np.array_equal(np.load(tmp_path / "b1" / "b.npy"), big["b"].numpy())

@@ -19,13 +19,13 @@ steps_of() { case $1 in c3) echo "--steps 20 --warmup 6";; c5) echo "--steps 20 
 for w in $what; do
   if [ $w = bench ]; then
     for c in $CFGS; do
-      timeout 900 python bench.py --config $c $(steps_of $c) > $out/bench_${c}_stdout.txt 2> $out/bench_${c}_stderr.txt
+      timeout 900 python bench.py --full --config $c $(steps_of $c) > $out/bench_${c}_stdout.txt 2> $out/bench_${c}_stderr.txt
       grep '^{' $out/bench_${c}_stdout.txt | tail -1 > $out/bench_$c.json; echo "bench $c rc=$? $(cut -c1-160 $out/bench_$c.json)"
     done
   elif [ $w = stats ]; then
     for c in $CFGS; do
       extra="--iwae-images 0 --cpu-baseline-steps 0 --no-amdahl --no-graph-profile"; [ $c = iwae ] && extra="--cpu-baseline-steps 0"
-      timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_$c -o $c -- python bench.py --config $c $(steps_of $c) $extra > $out/stats_${c}_stdout.txt 2>&1
+      timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_$c -o $c -- python bench.py --full --config $c $(steps_of $c) $extra > $out/stats_${c}_stdout.txt 2>&1
       echo "stats $c rc=$?"
     done
   elif [ $w = pmc ]; then
