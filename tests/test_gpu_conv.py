@@ -435,3 +435,183 @@ def test_plain_convolution_on_pixel_images_matches_float64(N, C, H, Co, stride, 
     assert (b.grad.double() - b64.grad).abs().max() <= 3e-6 * b64.grad.abs().max()
     if xgrad:
         assert (x.grad.double() - x64.grad).abs().max() <= 3e-6 * x64.grad.abs().max()
+
+
+# ---- the weight-gradient variants of the window kernels (csrc/evae_conv_win.hip: cw_wgrad_ok) -----------------------------------
+# cw_wgrad_ok(d, gated) picks one of eight kernel variants from the geometry alone (filter size, stride, output grid, merged output
+# channels CCq = 2 Co gated | Co plain): 1 = 5 x 5 stride 1; 2 / 5 / 6 = 3 x 3 stride 1 with a one-stage window, a four-stage one
+# (CCq <= 64), a two-stage one (CCq > 64); 3 = the 320-slot window (CCq <= 64, stride 1 on wide grids or stride 2); 4 = 3 x 3 stride 2
+# in 256 slots; 7 / 8 = stride 2 on wider grids, one channel group per launch (CCq <= 64 | <= 128).  Every row below names the
+# variant it must select and runs forward and backward against float64.
+def _cup16(c):
+    return (c + 15) // 16 * 16
+
+
+def _wgrad_descriptor(N, C, H, Co, k, s, kind):
+    """the gated descriptor whose evae_cw_supported(d, 2) is the variant of this layer's weight gradient: a gated layer's own (its
+    output channels zero-padded to a multiple of 32 when it closes a stack, GatedConvStackFn); for a plain or residual layer
+    cw_plain_ok / cw_res_ok call cw_wgrad_ok(d, 0) on the counts rounded up to 16, i.e. CCq = cup16(Co) -- a gated descriptor with
+    C' = cup16(C), Co' = cup16(Co) / 2"""
+    from evae import _lib
+    if kind == "gated":
+        return _lib.ConvDesc(N, C, H, H, (Co + 31) // 32 * 32, k, k, s, (k - 1) // 2)
+    return _lib.ConvDesc(N, _cup16(C), H, H, _cup16(Co) // 2, k, k, s, (k - 1) // 2)
+
+
+def _wgrad_variant(N, C, H, Co, k, s, kind):
+    import ctypes
+    from evae import _lib
+    return int(_lib.load().evae_cw_supported(ctypes.byref(_wgrad_descriptor(N, C, H, Co, k, s, kind)), 2))
+
+
+# (N, C, H, Co, k, stride, kind, variant): pixel counts N OH OW that are no multiple of 16 / 128 / 256, single images, channel
+# counts that are no multiple of 32
+_VARIANT_ROWS = [
+    (13, 32, 14, 32, 5, 1, "gated", 1),       # 13 x 14 x 14 = 2 548 pixels
+    (3, 32, 36, 32, 3, 1, "gated", 2),        # one-stage window, <= 64 merged channels
+    (1, 64, 37, 64, 3, 1, "gated", 2),        # ... 128 merged channels, one odd-sized image (1 369 pixels)
+    (2, 32, 40, 32, 3, 1, "gated", 3),
+    (9, 32, 28, 32, 3, 2, "gated", 3),
+    (11, 64, 14, 64, 3, 2, "gated", 4),       # 11 x 7 x 7 = 539 output pixels
+    (7, 32, 14, 32, 3, 1, "gated", 5),
+    (5, 48, 14, 24, 3, 1, "gated", 5),        # 48 input channels (an odd number of 16-channel groups), 24 outputs padded to 32
+    (5, 64, 14, 64, 3, 1, "gated", 6),
+    (3, 32, 64, 32, 3, 2, "gated", 7),        # stride 2 on the 64-grid, 64 merged channels
+    (1, 32, 64, 32, 3, 2, "gated", 7),
+    (2, 64, 32, 64, 3, 2, "gated", 8),
+    (1, 48, 36, 40, 3, 1, "plain", 2),
+    (3, 16, 40, 24, 3, 1, "plain", 3),
+    (9, 32, 28, 48, 3, 2, "plain", 3),
+    (11, 96, 14, 96, 3, 2, "plain", 4),
+    (33, 16, 16, 24, 3, 1, "plain", 5),
+    (7, 96, 14, 80, 3, 1, "plain", 6),
+    (5, 3, 64, 48, 3, 2, "plain", 7),         # fully_conv's first convolution (3 channels)
+    (1, 3, 64, 48, 3, 2, "plain", 7),
+    (20, 48, 32, 96, 3, 2, "plain", 8),       # its 48 -> 96 convolution
+    (1, 48, 36, 48, 3, 1, "res", 2),
+    (2, 96, 37, 96, 3, 1, "res", 2),
+    (3, 48, 40, 48, 3, 1, "res", 3),
+    (20, 48, 32, 48, 3, 1, "res", 5),         # fully_conv's residual blocks at c5 size
+    (70, 96, 16, 96, 3, 1, "res", 6),
+    (2, 48, 14, 48, 5, 1, "res", 1),          # a 5 x 5 residual block: the only un-gated layer variant 1 serves
+]
+
+
+def test_window_weight_gradient_variants_are_all_covered():
+    """Sweep the selector (3 x 3 and 5 x 5 filters, stride 1 and 2, grids 2 .. 128, merged channels 16 .. 128): the variants it can
+    return are exactly 1 .. 8, every one of them is selected by a row of _VARIANT_ROWS, with gating and without it wherever the code
+    allows (variant 1 is 5 x 5 only: un-gated, only a residual block reaches it -- the plain operators are 3 x 3).
+    A new variant, or a geometry change that moves a row to another variant, fails here until a case covers it."""
+    import ctypes
+    from evae import _lib
+    lib = _lib.load()
+    reachable = set()
+    for k in (3, 5):
+        for s in (1, 2):
+            for H in range(2, 129):
+                if s == 2 and H % 2:
+                    continue
+                for ccq in range(16, 129, 16):          # a gated descriptor with Co = CCq / 2: every merged width the predicate takes
+                    d = _lib.ConvDesc(4, 32, H, H, ccq // 2, k, k, s, (k - 1) // 2)
+                    reachable.add(int(lib.evae_cw_supported(ctypes.byref(d), 2)))
+    reachable.discard(0)
+    assert reachable == set(range(1, 9)), reachable
+    selected = {}
+    for N, C, H, Co, k, s, kind, want in _VARIANT_ROWS:
+        got = _wgrad_variant(N, C, H, Co, k, s, kind)
+        assert got == want, ((N, C, H, Co, k, s, kind), got, want)
+        selected.setdefault(kind == "gated", set()).add(got)
+    assert selected[True] == reachable, selected
+    assert selected[False] == reachable, selected
+
+
+def _variant_flags(N, C, H, Co, k, s, kind):
+    """what the library reports for a row: the window forward / data gradient (gated rows: on the padded output width the stack
+    uses), the plain and residual operators' predicates, and the channels-last path (whose thin-layer patch mode has no data
+    gradient)"""
+    import ctypes
+    from evae import _lib
+    lib = _lib.load()
+    d = _lib.ConvDesc(N, C, H, H, Co, k, k, s, (k - 1) // 2)
+    dg = _lib.ConvDesc(N, C, H, H, (Co + 31) // 32 * 32, k, k, s, (k - 1) // 2)
+    return dict(cw=[int(lib.evae_cw_supported(ctypes.byref(dg), w)) for w in (0, 1)],
+                cl=[int(lib.evae_conv2d_cl_supported(ctypes.byref(d), w, int(kind == "gated"))) for w in (0, 1, 2)],
+                plain=[int(lib.evae_cw_plain_supported(ctypes.byref(d), w)) for w in (0, 1, 2)],
+                res=int(lib.evae_cw_res_supported(ctypes.byref(d))))
+
+
+@pytest.mark.parametrize("N,C,H,Co,k,s,kind,want", _VARIANT_ROWS)
+def test_window_weight_gradient_variant_matches_float64(N, C, H, Co, k, s, kind, want, monkeypatch):
+    """One layer of each row of _VARIANT_ROWS forward and backward on the window kernels against torch float64 on the CPU: a gated layer
+    as the second layer of a GatedConvStackFn (same bars as test_gated_conv_stack_on_pixel_images_matches_float64), a plain convolution
+    through PlainConvFn (test_plain_convolution_on_pixel_images_matches_float64's), a residual block through ResStackFn
+    (test_residual_block_run_on_pixel_images_matches_float64's) -- with the weight gradient asserted to come from the window kernels."""
+    from evae import ops, _lib
+    assert _wgrad_variant(N, C, H, Co, k, s, kind) == want
+    flags = _variant_flags(N, C, H, Co, k, s, kind)
+    print((N, C, H, Co, k, s, kind), "variant", want, flags)
+    if kind == "gated":
+        assert flags["cw"] == [1, 1], flags
+    elif kind == "plain":
+        assert flags["plain"] == [1, 1, 1], flags
+    else:
+        assert flags["res"] == 1, flags
+    if C % 32 and C * k * k <= 64:                  # fully_conv's 3-channel first layer: the channels-last path could not take its data gradient
+        assert flags["cl"][1] == 0, flags
+    monkeypatch.setattr(ops, "RES_STACK_MIN_PIXELS", 1)
+    rs = np.random.RandomState(N * 1000 + C * 10 + H)
+    p = (k - 1) // 2
+    if kind == "gated":
+        l0 = [torch.from_numpy((rs.standard_normal(sh) * sc).astype(np.float32))
+              for sh, sc in (((C, 1, 3, 3), 0.6), ((C,), 0.2), ((C, 1, 3, 3), 0.6), ((C,), 0.2))]
+        l1 = [torch.from_numpy((rs.standard_normal(sh) * sc).astype(np.float32))
+              for sh, sc in (((Co, C, k, k), 1.5 / np.sqrt(C * k * k)), ((Co,), 0.2), ((Co, C, k, k), 1.5 / np.sqrt(C * k * k)), ((Co,), 0.2))]
+        x = torch.from_numpy((rs.rand(N, 1, H, H) < 0.3).astype(np.float32))
+        spec = [(l0[0].cuda(), 1, 1), (l1[0].cuda(), s, p)]
+        assert ops.conv_stack_depth((N, 1, H, H), spec) == 2
+        P64 = [t.double().requires_grad_(True) for t in l0 + l1]
+        h = x.double()
+        for (wh, bh, wg, bg), st, pd in ((P64[:4], 1, 1), (P64[4:], s, p)):
+            h = F.conv2d(h, wh, bh, st, pd) * torch.sigmoid(F.conv2d(h, wg, bg, st, pd))
+        gout = torch.from_numpy(rs.standard_normal(tuple(h.shape)).astype(np.float32))
+        h.backward(gout.double())
+        Pd = [t.cuda().requires_grad_(True) for t in l0 + l1]
+        with _lib.count_calls("evae_cw_") as n:
+            y = ops.gated_conv_stack(x.cuda(), [tuple(Pd[:4]) + (1, 1), tuple(Pd[4:]) + (s, p)])
+            y.backward(gout.cuda())
+            torch.cuda.synchronize()
+        assert n.get("evae_cw_bwd_weight", 0) >= 1, n
+        assert rel(y, h) < 2e-5, rel(y, h)
+        for i, (a, b) in enumerate(zip(Pd, P64)):
+            assert rel(a.grad, b.grad) < 3e-5, (i, rel(a.grad, b.grad))
+        return
+    x = torch.from_numpy((rs.standard_normal((N, C, H, H)) * (1.5 if kind == "res" else 1.0)).astype(np.float32))
+    w = torch.from_numpy((rs.standard_normal((Co, C, k, k)) / np.sqrt(C * k * k)).astype(np.float32))
+    b = torch.from_numpy((rs.standard_normal(Co) * 0.3).astype(np.float32))
+    x64, w64, b64 = (t.double().requires_grad_(True) for t in (x, w, b))
+    if kind == "res":
+        r = x64 + F.conv2d(F.elu(x64), w64, b64, 1, p)
+    else:
+        r = F.elu(F.conv2d(x64, w64, b64, s, p))
+    gout = torch.from_numpy(rs.standard_normal(tuple(r.shape)).astype(np.float32))
+    r.backward(gout.double())
+    xd, wd, bd = (t.cuda().requires_grad_(True) for t in (x, w, b))
+    with _lib.count_calls("evae_cw_") as n:
+        if kind == "res":
+            assert ops.res_stack_supported(xd, [wd])
+            y = ops.res_stack(xd, [(wd, bd)])
+        else:
+            assert ops.plain_conv_supported(xd, wd, s, 1)
+            y = ops.plain_conv(xd, wd, bd, s, elu=True)
+        y.backward(gout.cuda())
+        torch.cuda.synchronize()
+    if kind == "res":
+        assert n.get("evae_cw_res_run_bwd", 0) + n.get("evae_cw_bwd_weight_plain", 0) >= 1, n
+        assert rel(y, r) < 2e-5 and rel(xd.grad, x64.grad) < 2e-5, (rel(y, r), rel(xd.grad, x64.grad))
+        assert rel(wd.grad, w64.grad) < 3e-5 and rel(bd.grad, b64.grad) < 3e-5, (rel(wd.grad, w64.grad), rel(bd.grad, b64.grad))
+        return
+    assert n.get("evae_cw_bwd_weight_plain", 0) >= 1, n
+    assert (y.double().cpu() - r).abs().max() <= 2e-6 * r.abs().max()
+    for name, a, b_ in (("w", wd, w64), ("b", bd, b64), ("x", xd, x64)):
+        assert (a.grad.double().cpu() - b_.grad).abs().max() <= 3e-6 * b_.grad.abs().max(), \
+            (name, float((a.grad.double().cpu() - b_.grad).abs().max() / b_.grad.abs().max()))

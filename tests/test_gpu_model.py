@@ -1521,15 +1521,10 @@ def test_conv_two_level_step_at_c3_size_matches_the_oracle():
         assert np.abs(got - ref).max() <= 3e-4 * np.abs(ref).max(), (k, np.abs(got - ref).max() / np.abs(ref).max())
 
 
-def test_single_conv_training_step_at_c5_size():
-    """BASELINE configs[4] at its own size (VERDICT r03 weak #1: only c5's top-K and geometry were under test): `single_conv`
-    on 3 x 64 x 64, z = 256, approximate prior over 100 000 candidates drawn from a 100 000-image training set, k = 10, batch
-    100 -- one eager training step (cache of all latents, refresh of the batch's rows, top-K among the candidates' cached
-    latents, <= 1000 exemplars re-encoded, loss, backward) on the split-bf16 pipe and on the fp32-MFMA pipe: loss / RE / KL
-    finite and equal to 1e-5, every gradient norm to 1e-3; the step's top-K (batch means against the 100 000 cached latents,
-    reference models/BaseModel.py:263-264) bit-equal to the oracle's float64 scan with its (value, index) order; every batch row's KL
-    against the oracle's prior and posterior densities over the exemplar set the reference would re-encode (1e-4)."""
-    from evae import ops
+def _c5_case():
+    """BASELINE configs[4] at its own size: `single_conv` on 3 x 64 x 64, z = 256, approximate prior (k = 10) over 100 000 candidates
+    drawn from a 100 000-image training set (images with structure: a few prototypes + noise, so that neighbours in latent space
+    mean something), batch 100 -> (model, data on the device, dataset, device indices, the candidate draw, the step's eps)"""
     from utils.utils import importing_model
     from argparse import Namespace
     B, N, k = 100, 100000, 10
@@ -1543,7 +1538,6 @@ def test_single_conv_training_step_at_c5_size():
     model = importing_model(args)(args).cuda()
     model.train()
     g = torch.Generator(device="cuda"); g.manual_seed(9)
-    # images with structure (a few prototypes + noise) so that neighbours in latent space mean something
     protos = torch.randint(0, 256, (32, 12288), device="cuda", generator=g).float()
     which = torch.randint(0, 32, (N,), device="cuda", generator=g)
     data_dev = ((protos[which] * 0.7 + torch.randint(0, 77, (N, 12288), device="cuda", generator=g, dtype=torch.int16).float()).floor() + 0.5) / 256
@@ -1553,6 +1547,20 @@ def test_single_conv_training_step_at_c5_size():
     cand = torch.randperm(N, device="cuda", generator=g).cpu()    # the step's candidate draw (the reference: torch.randint on the host)
     rs = np.random.RandomState(12)
     eps = torch.from_numpy(rs.standard_normal((B, 256)).astype(np.float32)).cuda()
+    return model, data_dev, dataset, idx_all, cand, eps
+
+
+def test_single_conv_training_step_at_c5_size():
+    """BASELINE configs[4] at its own size (VERDICT r03 weak #1: only c5's top-K and geometry were under test): `single_conv`
+    on 3 x 64 x 64, z = 256, approximate prior over 100 000 candidates drawn from a 100 000-image training set, k = 10, batch
+    100 -- one eager training step (cache of all latents, refresh of the batch's rows, top-K among the candidates' cached
+    latents, <= 1000 exemplars re-encoded, loss, backward) on the split-bf16 pipe and on the fp32-MFMA pipe: loss / RE / KL
+    finite and equal to 1e-5, every gradient norm to 1e-3; the step's top-K (batch means against the 100 000 cached latents,
+    reference models/BaseModel.py:263-264) bit-equal to the oracle's float64 scan with its (value, index) order; every batch row's KL
+    against the oracle's prior and posterior densities over the exemplar set the reference would re-encode (1e-4)."""
+    from evae import ops
+    B, N, k = 100, 100000, 10
+    model, data_dev, dataset, idx_all, cand, eps = _c5_case()
     res = []
     # (pipe, window): the r05 path (pixel-image window kernels, one-launch weight norm) on both GEMM pipes, then the r04 kernels
     # (channels-last implicit GEMMs + torch's weight norm: the path the reference-generated goldens G9 / G19 / G20 / G21 pin at small
@@ -1610,6 +1618,204 @@ def test_single_conv_training_step_at_c5_size():
                         np.full((sel.numel(), 256), plv), sel.cpu().numpy(), test=False)
     log_q = orc.log_normal_diag(z.double().cpu().numpy(), mu.double().cpu().numpy(), lv.double().cpu().numpy())
     assert rel(res[0][0][2], log_q - log_p) < 1e-4, rel(res[0][0][2], log_q - log_p)
+
+
+# ---- single_conv restated in plain torch (any dtype, on the CPU): reference models/fully_conv.py:12-81, models/AbsModel.py:31-42,
+# utils/distributions.py (the oracle's formulas) -- the independent yardstick of the window operators at c5 size
+_LOG_2PI = float(orc.LOG_2_PI)
+_FC_ENC = ((("conv", 0, 2), ("elu",)) + tuple(("block", i) for i in range(2, 8)) + (("conv", 8, 2), ("elu",))
+           + tuple(("block", i) for i in range(10, 16)))
+_FC_DEC = ((("up",), ("conv", 1, 1), ("elu",)) + tuple(("block", i) for i in range(3, 9)) + (("up",), ("conv", 10, 1), ("elu",))
+           + tuple(("block", i) for i in range(12, 18)))
+
+
+def _fc_wn(T, name):
+    """weight_norm(dim=0): g * v / ||v||, the norm over every dimension but the first"""
+    v, g = T[name + ".weight_v"], T[name + ".weight_g"]
+    return g * v / v.reshape(v.shape[0], -1).norm(dim=1).reshape(-1, 1, 1, 1)
+
+
+def _fc_stack(T, prefix, spec, h):
+    import torch.nn.functional as F
+    for op in spec:
+        if op[0] == "conv":
+            nm = "%s.%d" % (prefix, op[1])
+            h = F.conv2d(h, _fc_wn(T, nm), T[nm + ".bias"], op[2], 1)
+        elif op[0] == "elu":
+            h = F.elu(h)
+        elif op[0] == "up":
+            h = F.interpolate(h, scale_factor=2, mode="nearest")
+        else:                                                  # residual block: x + conv(ELU(x))
+            nm = "%s.%d.conv1" % (prefix, op[1])
+            h = h + F.conv2d(F.elu(h), _fc_wn(T, nm), T[nm + ".bias"], 1, 1)
+    return h
+
+
+def _fc_q_z(T, x, isz, zdim, prior=False):
+    import torch.nn.functional as F
+    h = _fc_stack(T, "q_z_layers", _FC_ENC, x.reshape(-1, *isz))
+    mu = F.conv2d(h, _fc_wn(T, "q_z_mean"), T["q_z_mean.bias"], 1, 1).reshape(-1, zdim)
+    return mu if prior else (mu, F.conv2d(h, _fc_wn(T, "q_z_logvar"), T["q_z_logvar.bias"], 1, 1).reshape(-1, zdim))
+
+
+def _fc_p_x_mean(T, z, isz, bottleneck):
+    import torch.nn.functional as F
+    side = isz[1] // 4
+    h = _fc_stack(T, "p_x_layers", _FC_DEC, z.reshape(-1, bottleneck, side, side))
+    mean = F.conv2d(h, _fc_wn(T, "p_x_mean"), T["p_x_mean.bias"], 1, 1).clamp(1.0 / 512, 1.0 - 1.0 / 512)
+    return mean.reshape(z.shape[0], -1)
+
+
+def _t_log_normal_diag(x, mean, logvar):
+    return (-0.5 * (logvar + _LOG_2PI + (x - mean) ** 2 / torch.exp(logvar))).sum(1)
+
+
+def _t_log_logistic_256(x, mean, logvar):
+    b = 1.0 / 256.0
+    scale = torch.exp(logvar)
+    xs = (torch.floor(x / b) * b - mean) / scale
+    return torch.log(torch.sigmoid(xs + b / scale) - torch.sigmoid(xs) + 1e-7).sum(1)
+
+
+def _t_log_p_z(z, z_idx, centres, lv_row, c_idx):
+    """exemplar prior with the leave-one-out mask (reference models/BaseModel.py:98-128), distances expanded in the dtype of z"""
+    iv = torch.exp(-lv_row)
+    d = (z * z * iv).sum(1)[:, None] + (centres * centres * iv).sum(1)[None, :] - 2.0 * (z * iv) @ centres.t()
+    prob = -0.5 * (lv_row + _LOG_2PI).sum() - 0.5 * d
+    mask = torch.from_numpy(np.asarray(z_idx).reshape(-1, 1) == np.asarray(c_idx).reshape(1, -1)).to(z.device)
+    prob = prob.masked_fill(mask, float("-inf"))
+    den = float(centres.shape[0]) - mask.sum(1).to(z.dtype)
+    return torch.logsumexp(prob, 1) - torch.log(den)
+
+
+def _fc_step(T, x, eps, beta, isz, zdim, bottleneck, z_idx, c_idx, centres):
+    """per-row (loss, RE, KL) of one training step and (z, mu, logvar, log p(z)); `centres` [C x z]: the exemplar means"""
+    mu, lv = _fc_q_z(T, x, isz, zdim)
+    z = mu + eps * torch.exp(0.5 * lv)
+    mean = _fc_p_x_mean(T, z, isz, bottleneck)
+    RE = _t_log_logistic_256(x, mean, T["decoder_logstd"].expand_as(mean))
+    log_p = _t_log_p_z(z, z_idx, centres, T["prior_log_variance"].expand(zdim), c_idx)
+    KL = _t_log_normal_diag(z, mu, lv) - log_p
+    return -RE + beta * KL, RE, KL, (z, mu, lv, log_p)
+
+
+def test_single_conv_training_step_at_c5_size_matches_float64():
+    """BASELINE configs[4] at its own size held to float64, not to itself (the c5 test above compares the window path with the r04
+    path, and its gradient check is a norm: VERDICT "What's weak" 1).  The same case (_c5_case); one eager training step on the
+    split-bf16 pipe and on the fp32-MFMA pipe against a float64 torch restatement of reference models/fully_conv.py (weight norm,
+    residual blocks, strided convolutions, nn.Upsample(2), the clamped head) with the densities of evae_oracle (log_logistic_256,
+    log_normal_diag, the exemplar prior; the restated values are tied to the oracle's).  The exemplar set is the one the reference's
+    get_approximate_nearest_exemplars arrives at (models/BaseModel.py:256-271: the batch rows of the cache refreshed with their means,
+    top-k among the candidates' cached latents by the oracle's scan, `unique`); every exemplar row goes through the float64 encoder
+    (in chunks), forward and backward, and the GPU path's exemplar means are held to it at 1e-5.  Per-row loss / RE at 1e-4 relative,
+    per-row KL against the size of its terms at twice the float32 torch error, EVERY parameter's gradient element by element (max
+    error <= 3e-4 max |ref|); the window operators, and no layer-by-layer convolution, by counting the library calls."""
+    from evae import ops, _lib
+    import time
+    t_start = time.time()
+    B, N, k, beta = 100, 100000, 10, 0.5
+    isz, zdim = [3, 64, 64], 256
+    model, data_dev, dataset, idx_all, cand, eps = _c5_case()
+    xi = np.arange(500, 500 + B)
+    runs = []
+    for pipe in (1, 0):
+        ops.gemm_x6_configure(pipe, 2048)
+        orig, orig_qz = torch.randint, model.q_z
+        seen = {}
+
+        def spy(x, prior=False, rows=None):                    # the step's exemplar rows and means, and the batch's means
+            out = orig_qz(x, prior=prior, rows=rows)
+            if prior and rows is not None:
+                seen["rows"], seen["centres"] = rows.clone(), out[0].detach().clone()
+            elif not prior and rows is None and x.shape[0] == B:
+                seen["mu"] = out[0].detach().clone()
+            return out
+        try:
+            with torch.no_grad():
+                cache = tuple(t.clone() for t in model.cache_z(dataset))
+            cache_before = cache[0].clone()
+            torch.randint = lambda low=0, high=None, size=None, **kw: cand.clone()
+            model._draw_eps = lambda like: eps.reshape(like.shape)
+            model.q_z = spy
+            model.zero_grad()
+            with _lib.count_calls("evae_") as n:
+                loss, RE, KL = model.calculate_loss((data_dev[500:500 + B], idx_all[500:500 + B]), beta, average=False, cache=cache,
+                                                    dataset=dataset)
+                loss.mean().backward()
+                torch.cuda.synchronize()
+        finally:
+            torch.randint = orig
+            model.__dict__.pop("q_z", None)
+            ops.gemm_x6_configure(1, 2048)
+        # the window operators served the step: residual runs, plain convolutions (their weight gradients too), one-launch weight norm
+        assert n.get("evae_cw_res_run_fwd", 0) >= 6 and n.get("evae_cw_res_run_bwd", 0) >= 6, n
+        assert n.get("evae_cw_plain_fwd", 0) >= 6 and n.get("evae_cw_bwd_weight_plain", 0) >= 4, n
+        assert n.get("evae_weight_norm_set_fwd", 0) >= 2 and n.get("evae_weight_norm_set_bwd", 0) >= 2, n
+        assert not [f for f in n if f.startswith("evae_conv2d")], n      # no layer-by-layer convolution, either direction
+        # the exemplar set is the reference's: the oracle's top-k of the batch means among the refreshed candidates' cached rows
+        cache_before[500:500 + B] = seen["mu"]
+        _, near = orc.nearest_exemplars_topk(seen["mu"].double().cpu().numpy(), cache_before[cand.cuda()].double().cpu().numpy(), k)
+        sel = cand.numpy()[np.unique(near.reshape(-1))]
+        assert np.array_equal(seen["rows"].cpu().numpy(), sel)
+        del cache_before, cache
+        runs.append(dict(vals=[t.detach().double().cpu().numpy() for t in (loss, RE, KL)], sel=sel,
+                         centres=seen["centres"].double().cpu().numpy(),
+                         grads={k_: p.grad.double().cpu().numpy() for k_, p in model.named_parameters() if p.grad is not None}))
+    assert np.array_equal(runs[0]["sel"], runs[1]["sel"])
+    sel = runs[0]["sel"]
+    nsel = len(sel)
+    assert 10 <= nsel <= B * k
+    t_gpu = time.time() - t_start
+    # ---- float64 restatement on the same weights ----
+    T = {k_: v.detach().double().cpu().clone().requires_grad_(True) for k_, v in model.named_parameters()}
+    x64 = data_dev[500:500 + B].double().cpu()
+    CH = 128                                              # exemplar rows per pass of the float64 encoder (independent per image)
+
+    def rows64(i):
+        return data_dev[torch.from_numpy(sel[i:i + CH]).cuda()].double().cpu()
+    with torch.no_grad():
+        c64 = torch.cat([_fc_q_z(T, rows64(i), isz, zdim, prior=True) for i in range(0, nsel, CH)])
+    for r in runs:                                        # the GPU path's exemplar means against float64 (every row)
+        assert rel(r["centres"], c64.numpy()) < 1e-5, rel(r["centres"], c64.numpy())
+    centres = c64.clone().requires_grad_(True)
+    loss64, RE64, KL64, (z64, mu64, lv64, logp64) = _fc_step(T, x64, eps.double().cpu(), beta, isz, zdim, 1, xi, sel, centres)
+    # the restated densities are the oracle's
+    zn, mun, lvn, cn = (t.detach().numpy() for t in (z64, mu64, lv64, centres))
+    plv = float(T["prior_log_variance"].detach())
+    assert rel(logp64.detach().numpy(), orc.log_p_z(zn, xi.reshape(-1, 1), cn, np.full((nsel, zdim), plv), sel, test=False)) < 1e-6
+    assert rel((KL64 + logp64).detach().numpy(), orc.log_normal_diag(zn, mun, lvn)) < 1e-12
+    with torch.no_grad():
+        xm = _fc_p_x_mean(T, z64, isz, 1).numpy()
+    assert rel(RE64.detach().numpy(), orc.log_logistic_256(x64.numpy(), xm, np.full_like(xm, float(T["decoder_logstd"].detach())))) < 1e-12
+    loss64.mean().backward()
+    for i in range(0, nsel, CH):                          # d loss / d centres pulled back through the float64 exemplar encoder
+        _fc_q_z(T, rows64(i), isz, zdim, prior=True).backward(centres.grad[i:i + CH])
+    ref = {k_: t.grad.numpy().copy() for k_, t in T.items() if t.grad is not None}
+    # KL = log q(z | x) - log p(z) is a difference of two terms ~1e2 x its size, so a row's KL error is measured against the size of
+    # its terms, |log q| + |log p|, and held to twice what float32 torch (the reference's own arithmetic: same weights, float32
+    # exemplar means) makes on the same rows -- measured here, not assumed
+    logq64 = (KL64 + logp64).detach().numpy()
+    kscale = np.abs(logq64) + np.abs(logp64.detach().numpy())
+    T32 = {k_: v.detach().float() for k_, v in T.items()}
+    with torch.no_grad():
+        _, _, KL32, _ = _fc_step(T32, x64.float(), eps.cpu(), beta, isz, zdim, 1, xi, sel, c64.float())
+    e32 = float((np.abs(KL32.double().numpy() - KL64.detach().numpy()) / kscale).max())
+    worst = {"KL f32 torch": e32}
+    for pipe, r in zip((1, 0), runs):
+        for j, (what, rv) in enumerate((("loss", loss64), ("RE", RE64))):          # every row at 1e-4 relative
+            e = np.abs(r["vals"][j] - rv.detach().numpy()) / np.abs(rv.detach().numpy())
+            worst[(pipe, what)] = float(e.max())
+            assert e.max() <= 1e-4, (pipe, what, e.max())
+        e = float((np.abs(r["vals"][2] - KL64.detach().numpy()) / kscale).max())
+        worst[(pipe, "KL")] = e
+        assert e <= 2 * e32, (pipe, "KL", e, e32)
+        assert set(r["grads"]) == set(ref), (pipe, set(r["grads"]) ^ set(ref))
+        for k_, rg in ref.items():
+            e = float(np.abs(r["grads"][k_] - rg).max() / max(np.abs(rg).max(), 1e-30))
+            if e > worst.get((pipe, "grad"), (0.0, ""))[0]:
+                worst[(pipe, "grad")] = (e, k_)
+            assert e <= 3e-4, (pipe, k_, e)
+    print("c5 vs float64: %d exemplars, worst %s; GPU part %.1f s, all %.1f s" % (nsel, worst, t_gpu, time.time() - t_start))
 
 
 @pytest.mark.parametrize("upload", ["direct", "staged"])
