@@ -976,7 +976,7 @@ extern "C" int evae_gated_dense_bwd(const float* dout, int ldd, const float* out
 
 // dst[r][:] = scale[r] * src[idx[r]][:] (scale NULL: 1): the captured step's bridge between the distinct exemplar rows it encodes
 // and the draws the prior sees (centres of all draws from the distinct rows' encodings; a distinct row's head gradient from one
-// of its draws x its multiplicity -- evae/fused_vae.py::DEDUP).  z % 4 == 0, 16-byte aligned rows.
+// of its draws x its multiplicity -- evae/handoff.py: dedup).  z % 4 == 0, 16-byte aligned rows.
 __global__ __launch_bounds__(256) void gather_rows_kernel(const float4* __restrict__ src, const long long* __restrict__ idx,
                                                           const float* __restrict__ scale, unsigned n, unsigned z4,
                                                           float4* __restrict__ dst) {

@@ -24,17 +24,12 @@ import os
 import torch
 import torch.distributed as dist
 
-from . import _lib, ops, shard
+from . import _lib, handoff, ops, shard
 
 ACT_NONE, ACT_SIGMOID, ACT_HARDTANH = ops.ACT_NONE, ops.ACT_SIGMOID, ops.ACT_HARDTANH
 
 # generation of the staging rows behind a dataset buffer (keyed by its address): a second fused forward overwrites the rows a
 # pending backward would gather its batch from -- the backward checks that its forward was the last one to stage
-UNIT_UPSTREAM = [False]   # set by evae/graph.py around its step: the only backward is loss.backward(ones) on the batch mean
-WT_DONE = {}       # (wm, w2h, w2g) pointers -> (wT of the head, wT of layer 2) the step's head launch just wrote
-P6_LAST = [None]   # (w2h ptr, w2g ptr, H, forward image, data-gradient image) of the last step that took the pre-split layer 2
-P6_DONE = {}       # (w2h ptr, w2g ptr) -> True when the step's head launch just built both images (evae/graph.py)
-PREP_DONE = {}     # prepared-weights buffer -> (w1h, w1g) pointers it was just filled from, by the step's head launch
 _STAGE_GEN = {}
 _XT_GEN = {}       # workspace pointer -> generation of the transposed byte rows the forward pass left there
 _ZEROED = {}      # workspace name -> (address, shape) it was last zero-filled for
@@ -107,12 +102,11 @@ PARAM_ORDER = [
 ]
 
 
-# The duplicates among the exemplar draw, set by the captured step's runner around its forward pass (evae/graph.py): None, or
+# The duplicates among the exemplar draw, the `dedup` field of the step's hand-off (evae/handoff.py; set by evae/graph.py): None, or
 # (draws [C] int64, inv [C] int64, rep [Cl] int64, mult [Cl] fp32) with ex_idx = the Cl DISTINCT rows (padded, multiplicity 0).  The
 # encoder then runs over the distinct rows only; the prior sees all C draws -- centres gathered through inv, leave-one-out mask on
 # the draws' indices -- and a distinct row's head gradient is mult x the gradient of ONE of its draws (duplicates have identical
 # centres, hence identical prior gradients).  Same loss, same gradients as encoding every draw (reference models/BaseModel.py:243-254).
-DEDUP = [None]
 
 
 def _vp(v):
@@ -213,6 +207,7 @@ class VaeExactLoss(torch.autograd.Function):
         k = _K(dev)
         lib = k.lib
         B, D = x.shape
+        ho = handoff.current() or handoff.StepHandoff()       # what the step's runner says about this step; nothing without one
         # approximate prior (reference models/BaseModel.py:256-271): ex_idx holds the CANDIDATE draw; the exemplar rows are the
         # B * k static slots picked by the top-K over the cached latents of the candidates (repeats masked, evae_select_exemplars)
         approx = approx_cache is not None
@@ -291,7 +286,7 @@ class VaeExactLoss(torch.autograd.Function):
         if u8:
             # both first-layer launches read the weights as three bf16 terms in tile order: split once, in front of the fork
             prep = k.ws("u8prep", lib.evae_dense_u8_prepared_bytes(H, D))
-            if PREP_DONE.pop(prep.data_ptr(), None) != (w1h.data_ptr(), w1g.data_ptr()):
+            if not ho.take_prep(prep.data_ptr(), w1h.data_ptr(), w1g.data_ptr()):
                 # (the captured step's head launch -- evae/graph.py -- does this split beside its batch prologue and says so)
                 _lib.check(lib.evae_dense_u8_prepare(_vp(w1h), _vp(w1g), H, D, _vp(prep), prep.numel(), k.st), "u8_prepare")
             side.wait_stream(main)
@@ -332,11 +327,11 @@ class VaeExactLoss(torch.autograd.Function):
         lv_row = torch.empty(Z, **f32)                     # the prior's log-variance row
         beta_dev = beta if torch.is_tensor(beta) else None
         beta_host = 0.0 if beta_dev is not None else float(beta)
-        dd = DEDUP[0]
+        dd = ho.dedup
         if dd is not None and (approx or dd[2].numel() != Cl or dd[3].numel() != Cl):
             raise _lib.EvaeError("fused step: the duplicate tables do not belong to this exemplar set")
         Cp = dd[0].numel() if dd is not None else Cl          # exemplars the prior sees (all draws; this rank's when sharded)
-        prior_train = bool(PRIOR_TRAIN and UNIT_UPSTREAM[0] and average and not sharded and Cl > 0 and not ONE_STREAM[0]
+        prior_train = bool(PRIOR_TRAIN and ho.unit_upstream and average and not sharded and Cl > 0 and not ONE_STREAM[0]
                            and ops.prior_train_applies(B, Cp, Z))
         coef = None
         with torch.cuda.stream(side):
@@ -350,8 +345,8 @@ class VaeExactLoss(torch.autograd.Function):
             if p6:
                 # layer 2's weights as images (they change every step); the main stream meets them behind the first layer --
                 # unless the captured step's head launch built them (evae/graph.py: two launches and one join less)
-                P6_LAST[0] = (w2h.data_ptr(), w2g.data_ptr(), H, w2_img, w2t_img)
-                if not P6_DONE.pop((w2h.data_ptr(), w2g.data_ptr()), False):
+                ho.p6_images = (w2h.data_ptr(), w2g.data_ptr(), H, w2_img, w2t_img)
+                if not ho.take_p6(w2h.data_ptr(), w2g.data_ptr()):
                     _lib.check(lib.evae_p6_pack_rows(_vp(w2h), _vp(w2g), H, H, H, 1, _vp(w2_img), w2_img.numel(), kd.st), "p6_pack_rows")
                     _lib.check(lib.evae_p6_pack_cols(_vp(w2h), _vp(w2g), H, H, H, -1, lib.evae_p6_nks(2 * H), _vp(w2t_img),
                                                      w2t_img.numel(), kd.st), "p6_pack_cols")
@@ -520,7 +515,7 @@ class VaeExactLoss(torch.autograd.Function):
             R, ldp = ns.value, B
             pm = w.data_ptr(); ps = pm + 4 * prow.value * B; pn = ps + 4 * prow.value * B
         # captured step (unit upstream promise) on one device: merge on the main stream, ELBO assembly on the side stream
-        elbo_split = bool(ELBO_SPLIT and UNIT_UPSTREAM[0] and average and not sharded and xt_late and not ONE_STREAM[0])
+        elbo_split = bool(ELBO_SPLIT and ho.unit_upstream and average and not sharded and xt_late and not ONE_STREAM[0])
         if prior_train or elbo_split:
             pass                             # the main stream does not meet the reconstruction term at all
         elif xt_late:
@@ -545,7 +540,7 @@ class VaeExactLoss(torch.autograd.Function):
                 side.wait_event(merged)
                 _lib.check(lib.evae_elbo_assemble(_vp(logp), _vp(RE), _vp(logq), _vp(beta_dev), beta_host, B, _vp(loss), _vp(KL),
                                                   _vp(means), kd.st), "elbo_assemble")
-        elif UNIT_UPSTREAM[0] and average and not sharded:
+        elif ho.unit_upstream and average and not sharded:
             # the caller (evae/graph.py) promises loss.backward(ones) on the batch mean and nothing else: the backward pass's
             # coefficient vectors are then known here (-1/B, beta/B, -beta/B) and its elbo_bwd launch is not needed
             coef = (torch.empty(B, **f32), torch.empty(B, **f32), torch.empty(B, **f32))
@@ -563,7 +558,7 @@ class VaeExactLoss(torch.autograd.Function):
         ctx.elbo_keep = (RE, logq, logp, loss, KL, means) if (elbo_split or prior_train) else None
         ctx.prior_done = prior_done
         ctx.dd = (dd, centres_p) if (dd is not None and not prior_train) else None
-        ctx.wt = WT_DONE.pop((wm.data_ptr(), w2h.data_ptr(), w2g.data_ptr()), None)
+        ctx.wt = ho.take_wt(wm.data_ptr(), w2h.data_ptr(), w2g.data_ptr())
         ctx.set_materialize_grads(False)       # unused outputs (RE, KL) then arrive as None, not as zero-filled tensors
         ctx.k_dev = dev
         ctx.dims = (B, D, H, Z, Cl, Mp, ldd, beta, int(sharded))

@@ -15,7 +15,13 @@ them uploaded instead).  The gather, the dynamic binarisation and the eps of the
 counter-based generator (evae_batch_prologue: seed = torch's seed when the runner is built, counter = step number, both
 in the control block); whatever else draws random numbers uses the CUDA generator, which torch registers with the
 capture so that every replay advances its Philox offset.  RCCL collectives of the sharded prior are captured too.
+
+What the model and the fused node have to know about the step that is running -- its gather list, the distinct-row tables, the
+prologue's eps, the promise that the only backward is loss.backward(ones), what the head launch already did for them -- travels
+on ONE object, evae/handoff.py's StepHandoff: _step_scope installs it for the length of a call and takes it away again, so
+nothing of a step outlives it.
 """
+import contextlib
 import ctypes as C
 import math
 import os
@@ -24,7 +30,7 @@ import sys
 
 import torch
 
-from . import _lib, ops, shard
+from . import _lib, fused_vae, handoff, ops, shard
 
 
 _REFRESH_PROF = os.environ.get("EVAE_REFRESH_PROF") == "1"       # host time of _refresh by part, printed at exit (tools/host_time.py)
@@ -82,11 +88,10 @@ class GraphedTrainStep:
         # gather list holds the DISTINCT rows only -- `cap` of them, a fixed count the distinct rows of a draw stay under by
         # five standard deviations (eight until r06), padded with multiplicity 0 -- and the block carries the draw itself, every draw's
         # position among the distinct rows, one draw per distinct row and the multiplicities behind its scalars
-        # (evae_host_dedup on the host; evae/fused_vae.py::DEDUP for what the step does with them).  EVAE_DEDUP=0: off.
+        # (evae_host_dedup on the host; evae/handoff.py's `dedup` for what the step does with them).  EVAE_DEDUP=0: off.
         self.dedup = None
         Cd = Cl                                  # rows of the gather list's head
         Nt = int(a.training_set_size)
-        from . import fused_vae as _fv0
         sharded = model._sharded()
         want = (os.environ.get("EVAE_DEDUP", "1") != "0" and (Cl == C or sharded) and Cl > 0 and not a.approximate_prior and Nt > 0
                 and a.prior == 'exemplar_prior' and int(a.z1_size) % 4 == 0)
@@ -94,7 +99,7 @@ class GraphedTrainStep:
             # the fused node on one device: what it does with the tables needs the byte store and the one-launch prior of a captured
             # step (the same predicate as there).  A sharded fused step gathers the per-draw centres for the prior's own kernels (r06);
             # every other model meets the tables in get_exemplar_set (models/BaseModel.py, ops.ExpandRowsFn)
-            want = (self.u8 and os.environ.get("EVAE_UNIT_UPSTREAM", "1") != "0" and _fv0.PRIOR_TRAIN and not _fv0.ONE_STREAM[0]
+            want = (self.u8 and os.environ.get("EVAE_UNIT_UPSTREAM", "1") != "0" and fused_vae.PRIOR_TRAIN and not fused_vae.ONE_STREAM[0]
                     and ops.prior_train_applies(self.B, C, int(a.z1_size)))
         if want:
             # distinct rows among the Cl draws of this process (all C on one device, its shard of the common draw otherwise) from Nt:
@@ -188,6 +193,7 @@ class GraphedTrainStep:
         self.cache = None          # approximate prior: the latent cache in static buffers (set_cache)
         self.graph = None
         self.failed = False
+        self._p6_last = None       # what the fused node of this runner's last step reported (handoff.StepHandoff.p6_images)
         self._overflow = None      # set by _refresh when a draw has more distinct rows than the captured step holds: (draws | staging rows)
         self.overflow_steps = 0
         self.eager_opt = False     # True: the participants' step counts differ (resumed checkpoint): eager optimizer steps only
@@ -208,10 +214,9 @@ class GraphedTrainStep:
                 dst.copy_(src.detach())
         return self.cache
 
-    def _first_layer_split(self):
+    def _first_layer_split(self, h):
         """(w1h, w1g, prepared buffer) when the fused step on the byte store will run: its weight split then rides in the
-        prologue's launch (one launch at the head of the step instead of two); None otherwise."""
-        from . import fused_vae
+        prologue's launch (one launch at the head of the step instead of two); None otherwise.  Says so on the hand-off `h`."""
         m = self.model
         if os.environ.get("EVAE_HEAD_MERGE", "1") == "0" or not (m._fused_config() and not m._sharded()):
             return None
@@ -222,7 +227,7 @@ class GraphedTrainStep:
         lib = fused_vae._lib.load()
         H, D = wh.shape
         prep = ops._workspace("u8prep", lib.evae_dense_u8_prepared_bytes(H, D), wh.device)
-        fused_vae.PREP_DONE[prep.data_ptr()] = (wh.data_ptr(), wg.data_ptr())
+        h.prep = (prep.data_ptr(), wh.data_ptr(), wg.data_ptr())
         # the transposed weights the two large data gradients of the backward pass read on the split-bf16 kernel
         jobs = []
         Cl = getattr(self, "_Cd", self.hi - self.lo)      # the rows the fused node encodes (the distinct ones of a draw when dedup is on)
@@ -234,18 +239,18 @@ class GraphedTrainStep:
                 nb2 = lib.evae_dense_bwd_data_wt_bytes(w2h.shape[0], w2h.shape[1], 2)
                 self._wt_bufs = (torch.empty(nb1, dtype=torch.uint8, device=wh.device), torch.empty(nb2, dtype=torch.uint8, device=wh.device))
             jobs = [(wm.detach(), None, self._wt_bufs[0]), (w2h.detach(), w2g.detach(), self._wt_bufs[1])]
-            fused_vae.WT_DONE[(wm.data_ptr(), w2h.data_ptr(), w2g.data_ptr())] = self._wt_bufs
+            h.wt = ((wm.data_ptr(), w2h.data_ptr(), w2g.data_ptr()), self._wt_bufs)
         # layer 2's weight images of the pre-split GEMMs (fused_vae's p6 path, when the last step took it): built by the head
         # launch too -- they depend on the weights alone -- instead of two launches on the side stream and a join in front of
         # layer 2's forward GEMM (rides with the control block's hand-over: evae_batch_prologue_u8_step)
         packs = []
-        last = fused_vae.P6_LAST[0]
+        last = self._p6_last
         if (os.environ.get("EVAE_P6_HEAD", "1") != "0" and self._handover and self.by_index and last is not None
                 and w2h is not None and w2g is not None and last[:2] == (w2h.data_ptr(), w2g.data_ptr())):
             H2, w2_img, w2t_img = last[2], last[3], last[4]
             packs = [(0, w2h.detach(), w2g.detach(), H2, H2, H2, 1, 0, w2_img),
                      (1, w2h.detach(), w2g.detach(), H2, H2, H2, -1, lib.evae_p6_nks(2 * H2), w2t_img)]
-            fused_vae.P6_DONE[(w2h.data_ptr(), w2g.data_ptr())] = True
+            h.p6 = (w2h.data_ptr(), w2g.data_ptr())
         return wh.detach(), wg.detach(), prep, jobs, packs
 
     # the body that gets captured
@@ -261,6 +266,7 @@ class GraphedTrainStep:
         return t
 
     def _body(self, eager_opt=False, tables=None):
+        h = handoff.current()                     # (this call's: _step_scope)
         if self.by_index:
             # the batch is rows `idx` of the HBM-resident dataset: gathered (and binarised) straight into the staging rows
             # of the fused step, no image bytes cross PCIe
@@ -271,7 +277,7 @@ class GraphedTrainStep:
                     job = (self._d_ctl[0], self._d_ctl[1], self.ctl, self._ho_state, self._o_idx, self._o_seed)
                     if not torch.cuda.is_current_stream_capturing():
                         self._ho_state[:1].copy_(self._ho_par[self._calls & 1])     # (eager: the block this call uploaded)
-                prep = self._first_layer_split()
+                prep = self._first_layer_split(h)
                 ops.batch_prologue_u8(self.data_rows, self.idx_flat, self.binarize, self.seed_ctr, self.x_div, x,
                                       self.stage_rows, self.eps_buf, prepare=prep, ctl_job=job,
                                       packs=prep[4] if (prep is not None and job is not None) else None)
@@ -281,22 +287,9 @@ class GraphedTrainStep:
         else:
             x = torch.bernoulli(self.x_in) if self.binarize else self.x_in
         self.opt.zero_grad(set_to_none=True)      # backward then installs the fused node's gradient buffers
-        from . import fused_vae as _fv
-        _fv.UNIT_UPSTREAM[0] = os.environ.get("EVAE_UNIT_UPSTREAM", "1") != "0"     # the backward below is loss.backward(ones), nothing else
-        ops.STEP_BETA[0] = self.beta if _fv.UNIT_UPSTREAM[0] else None              # (the modular paths' prior: ops.prior_logp)
-        _fv.DEDUP[0] = self.dedup["tables"] if self.dedup is not None else None
-        try:
-            loss, RE, KL = self.model.calculate_loss((x, self.idx_in), self.beta, average=True, dataset=self.dataset,
-                                                     cache=self.cache)
-        finally:
-            _fv.UNIT_UPSTREAM[0] = False
-            _fv.DEDUP[0] = None
-            ops.STEP_BETA[0] = None
-        if self.by_index and self.u8:
-            from . import fused_vae
-            fused_vae.PREP_DONE.clear()           # (a token the fused step did not consume must not outlive this step)
-            fused_vae.WT_DONE.clear()
-            fused_vae.P6_DONE.clear()
+        h.unit_upstream = os.environ.get("EVAE_UNIT_UPSTREAM", "1") != "0"     # the backward below is loss.backward(ones), nothing else
+        h.beta = self.beta if h.unit_upstream else None                        # (the modular paths' prior: ops.prior_logp)
+        loss, RE, KL = self.model.calculate_loss((x, self.idx_in), self.beta, average=True, dataset=self.dataset, cache=self.cache)
         with ops.deferred_wgrads(loss):          # thin layers' weight gradients behind the backward pass, grouped (evae/ops.py)
             loss.backward(gradient=self._one)
         # the step's statistics ride in the optimizer's last launch (evae_adam_normgrad_step_stats)
@@ -402,39 +395,39 @@ class GraphedTrainStep:
         form) -- issued launch by launch instead of replayed: bench.py brackets its large launches with HIP events this way (event
         pairs cannot be read back from inside a replayed graph).  Only after the graph exists."""
         assert self.graph is not None, "step_eagerly: the step has not been captured yet"
-        self.model._exemplar_indices_override = (self.rows, self._Cd)
-        self.model._exemplar_dedup = self.dedup["tables"] if self.dedup is not None else None
-        try:
-            self._refresh(data, indices, beta)
-            self.model._eps_override = self.eps_buf if self.by_index else None
-            self.model._batch_staged = bool(self.by_index and self.u8)
+        with self._step_scope(self.rows, self._Cd, self.dedup and self.dedup["tables"], refresh=(data, indices, beta)):
             if self._overflow is not None:
                 return self._every_draw_step()
             self._body(eager_opt=self.eager_opt, tables=self._eager_tables())
             self._calls += 1
             return self.out
-        finally:
-            if self._handover and self.by_index:
-                self._ev_used[self._k_used].record()      # (staging block k was read by this step's first launch)
-            self.model._exemplar_indices_override = None
-            self.model._exemplar_dedup = None
-            self.model._eps_override = None
-            self.model._batch_staged = False
+
+    @contextlib.contextmanager
+    def _step_scope(self, rows, n_rows, dedup, refresh=None):
+        """The hand-off of one step (evae/handoff.py) around the block, and the ONE place that tears a step down.  `refresh` =
+        (data, indices, beta) for the scope of a whole call: it uploads the call's control block first and, at the end, marks
+        the staging block as read; None for the every-draw step inside such a call."""
+        h = handoff.StepHandoff(rows, n_rows, dedup)
+        with handoff.active(h):
+            try:
+                if refresh is not None:
+                    self._refresh(*refresh)
+                h.eps = self.eps_buf if self.by_index else None
+                h.batch_staged = bool(self.by_index and self.u8)
+                yield h
+            finally:
+                if refresh is not None and self._handover and self.by_index:
+                    self._ev_used[self._k_used].record()      # (staging block k was read by this step's first launch)
+                self._p6_last = h.p6_images or self._p6_last
 
     def _every_draw_step(self):
         """One step issued eagerly with EVERY draw encoded (no distinct-row tables): what a draw that does not fit the captured
         step's fixed row count gets instead of an exception.  Same control block (batch, seed, beta, step sizes), same optimizer form."""
         rows_ext, self._overflow = self._overflow, None
-        Cl = self.hi - self.lo
-        self.model._exemplar_indices_override = (rows_ext, Cl)
-        self.model._exemplar_dedup = None
-        dd, self.dedup = self.dedup, None
-        try:
+        with self._step_scope(rows_ext, self.hi - self.lo, None):
             self._body(eager_opt=self.eager_opt or self._calls == 0, tables=self._eager_tables() if self.graph is not None else None)
             if self._calls == 0 and not self.eager_opt and not self.opt.learn_members(self._adam_tables):
                 self.failed = self.eager_opt = True
-        finally:
-            self.dedup = dd
         self._calls += 1
         self.overflow_steps += 1
         return self.out
@@ -445,12 +438,7 @@ class GraphedTrainStep:
             # this graph's launches read the step size from ITS control block (another runner on the same optimizer has its own)
             self._adam_tables["step_size"] = [self.scal[1 + g:2 + g] for g in range(self.ngroups)]
             self.opt.enable_graph_mode(storage=self._adam_tables["step_size"])
-        self.model._exemplar_indices_override = (self.rows, self._Cd)
-        self.model._exemplar_dedup = self.dedup["tables"] if self.dedup is not None else None
-        try:
-            self._refresh(data, indices, beta)
-            self.model._eps_override = self.eps_buf if self.by_index else None
-            self.model._batch_staged = bool(self.by_index and self.u8)
+        with self._step_scope(self.rows, self._Cd, self.dedup and self.dedup["tables"], refresh=(data, indices, beta)):
             if self._overflow is not None:
                 return self._every_draw_step()
             if self.graph is None:
@@ -512,10 +500,3 @@ class GraphedTrainStep:
             if shard.is_active() and self._calls % shard.REPLICA_CHECK_EVERY == 0:
                 shard.check_replicas(self.model.parameters())      # (replica mode's guard: raises when the ranks drifted apart)
             return self.out
-        finally:
-            if self._handover and self.by_index:
-                self._ev_used[self._k_used].record()      # (staging block k was read by this step's first launch)
-            self.model._exemplar_indices_override = None
-            self.model._exemplar_dedup = None
-            self.model._eps_override = None
-            self.model._batch_staged = False

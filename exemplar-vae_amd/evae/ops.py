@@ -7,7 +7,7 @@ import os
 
 import torch
 
-from . import _lib
+from . import _lib, handoff
 
 ACT_NONE, ACT_SIGMOID, ACT_HARDTANH = 0, 1, 2
 TOPK_SQRT = 1
@@ -337,12 +337,11 @@ class PriorLogP(torch.autograd.Function):
 
 # The captured step's promise (evae/graph.py): the loss is mean_i(beta KL_i - RE_i) with log p(z_i) entering KL_i with coefficient
 # -1, and what follows is loss.backward(ones) -- so d loss / d log p(z_i) = -beta / B is known in the forward pass.  The runner
-# puts its beta (device scalar) here around calculate_loss + backward; None: no promise.
-STEP_BETA = [None]
+# puts its beta (device scalar) on the step's hand-off (evae/handoff.py: `beta`); None, or no hand-off: no promise.
 
 
 class PriorLogPTrain(torch.autograd.Function):
-    """PriorLogP under STEP_BETA's promise: forward partials, merge and backward in ONE launch (evae_prior_train_step,
+    """PriorLogP under the promise of the hand-off's `beta`: forward partials, merge and backward in ONE launch (evae_prior_train_step,
     csrc/evae_prior_train.h); backward() hands out the gradients the forward pass computed (EVAE_PRIOR_TRAIN_CHECK=1: after
     checking the upstream gradient against -beta / B)."""
 
@@ -365,8 +364,9 @@ class PriorLogPTrain(torch.autograd.Function):
 
 
 def prior_logp(z, centres, log_var_row, z_idx, c_idx):
-    """log p(z) [B] of ONE device's exemplars, differentiable: PriorLogP, or its one-launch training form under STEP_BETA"""
-    beta = STEP_BETA[0]
+    """log p(z) [B] of ONE device's exemplars, differentiable: PriorLogP, or its one-launch training form under the hand-off's `beta`"""
+    h = handoff.current()
+    beta = h.beta if h is not None else None
     if (beta is not None and torch.is_grad_enabled() and z.is_cuda and z.dim() == 2 and centres.dim() == 2
             and z.dtype == torch.float32 and centres.dtype == torch.float32 and z.is_contiguous() and centres.is_contiguous()
             and (z.data_ptr() | centres.data_ptr()) % 16 == 0 and prior_train_applies(z.shape[0], centres.shape[0], z.shape[1])):

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from evae import fused_vae, ops, shard
+from evae import fused_vae, handoff, ops, shard
 from utils.distributions import (log_bernoulli, log_normal_diag, log_normal_standard, log_logistic_256,
                                  log_normal_diag_vectorized)
 from utils.nn import NonLinear, he_init, normal_init
@@ -96,23 +96,23 @@ class BaseModel(nn.Module, ABC):
         C = a.number_components
         sharded = self._sharded()
         lo, hi = shard.bounds(C) if sharded else (0, C)
-        override = getattr(self, '_exemplar_indices_override', None)
-        rows_ext = None
-        eager_dd = None
-        if isinstance(override, tuple):   # graph-captured step: (gather list [local exemplars | staging rows], #local)
-            rows_ext, n_local = override
-            ex_local = rows_ext[:n_local]
-        elif override is not None:        # indices drawn into a static device buffer
-            ex_local = override[lo:hi]
+        # the step runner's word about this step (evae/graph.py), looked up once; an eager step carries a hand-off of its own
+        # (bench.py still clears a `_exemplar_indices_override` on the model: that attribute is no longer read)
+        h = handoff.current() or handoff.StepHandoff()
+        if h.rows is not None:            # graph-captured step: gather list [local exemplars | staging rows], #local
+            ex_local = h.rows[:h.n_rows]
         else:
             exemplars_indices = torch.randint(low=0, high=a.training_set_size, size=(C,))   # reference :245
             eager_dd = self._dedup_draws(exemplars_indices[lo:hi]) if not exemplars_indices.is_cuda else None
-            ex_local = eager_dd[0] if eager_dd is not None else self._indices_to_device(exemplars_indices[lo:hi])
+            if eager_dd is not None:
+                ex_local, h.dedup = eager_dd       # (the distinct rows; their tables reach the node's forward on the hand-off)
+            else:
+                ex_local = self._indices_to_device(exemplars_indices[lo:hi])
         # the image store the exemplar rows are gathered from: bytes when the data are k/255 (4x less HBM, and the first
         # layer then runs on the bf16 matrix pipe, csrc/evae_dense_u8.hip), fp32 rows otherwise
         u8 = self.resident_u8(dataset, x.shape[0])
         x2 = x.reshape(x.shape[0], -1).float()
-        if u8 is not None and not getattr(self, '_batch_staged', False) and not torch.cuda.is_current_stream_capturing():
+        if u8 is not None and not h.batch_staged and not torch.cuda.is_current_stream_capturing():
             # eager call: the batch goes into the byte store's staging rows as round(255 x), so x itself has to be k/255 (what
             # the loaders and dynamic binarisation hand out); a batch that is not -- augmented, noisy -- takes the fp32 store
             # for this call instead of being quantised silently (a capture cannot read a flag back: the captured step checks its
@@ -137,26 +137,19 @@ class BaseModel(nn.Module, ABC):
         if a.training_set_size > n_data:
             # the reference's dataset.tensors[0][exemplars_indices] raises here; the row-gather GEMM would read staging rows
             raise IndexError("training_set_size %d exceeds the %d rows of the dataset" % (a.training_set_size, n_data))
-        eps = getattr(self, '_eps_override', None)          # the captured step draws eps in its prologue launch
+        # the captured step draws eps in its prologue launch; `_eps_override` is the noise hook of a model without a runner (tests)
+        eps = h.eps if h.eps is not None else getattr(self, '_eps_override', None)
         if eps is None or tuple(eps.shape) != (x2.shape[0], a.z1_size):
             eps = self._draw_eps(torch.empty((x2.shape[0], a.z1_size), device=x.device))
         named = dict(self.named_parameters())
         params = [named[n] for n in fused_vae.PARAM_ORDER]
         beta = beta if torch.is_tensor(beta) else float(beta)
-        staged = bool(getattr(self, '_batch_staged', False))      # the captured step has put the batch into the staging rows
         approx_cache = cache[0] if a.approximate_prior else None  # ex_local is then the candidate draw (reference :258)
-        if eager_dd is not None:
-            fused_vae.DEDUP[0] = eager_dd[1]           # read by the node's forward; the runner of a captured step sets its own
-            try:
-                return fused_vae.VaeExactLoss.apply(x2, x_indices.reshape(-1), data_ext, n_data, ex_local, C, eps,
-                                                    beta, (2 if getattr(a, 'shard_batch', False) else 1) if sharded else 0,
-                                                    bool(a.no_mask), bool(average), None, staged, None, int(a.approximate_k), *params)
-            finally:
-                fused_vae.DEDUP[0] = None
-        return fused_vae.VaeExactLoss.apply(x2, x_indices.reshape(-1), data_ext, n_data, ex_local, C, eps,
-                                            beta, (2 if getattr(a, 'shard_batch', False) else 1) if sharded else 0,
-                                            bool(a.no_mask), bool(average), None if a.approximate_prior else rows_ext, staged,
-                                            approx_cache, int(a.approximate_k), *params)
+        with handoff.active(h):           # (the runner's, which is active already, or this eager step's own)
+            return fused_vae.VaeExactLoss.apply(x2, x_indices.reshape(-1), data_ext, n_data, ex_local, C, eps,
+                                                beta, (2 if getattr(a, 'shard_batch', False) else 1) if sharded else 0,
+                                                bool(a.no_mask), bool(average), None if a.approximate_prior else h.rows, h.batch_staged,
+                                                approx_cache, int(a.approximate_k), *params)
 
     def calculate_loss(self, x, beta=1., average=False, exemplars_embedding=None, cache=None, dataset=None):
         x, x_indices = x
@@ -510,7 +503,7 @@ class BaseModel(nn.Module, ABC):
         DISTINCT rows among them, padded to a multiple of `pad` with multiplicity 0; tables (draws, inv, rep, mult) on the device) --
         or None when duplicates are rare (< 8 % of the draws), the set is small, or EVAE_DEDUP / EVAE_DEDUP_EAGER = 0.  The eager
         counterpart of the captured step's distinct-row tables (evae/graph.py): the encoder runs over `rows`, the prior still sees
-        every draw (evae.ops.expand_rows / evae/fused_vae.py::DEDUP), the loss and gradients are those of encoding every draw.  Works
+        every draw (evae.ops.expand_rows / the `dedup` field of evae/handoff.py), the loss and gradients are those of encoding every draw.  Works
         per shard: a rank deduplicates ITS slice of the common draw (r06; VERDICT r05 missing #2)."""
         a = self.args
         Cl = int(local_cpu.numel())
@@ -547,13 +540,12 @@ class BaseModel(nn.Module, ABC):
     # ------------------------------------------------------------------ exemplar sets
     def get_exemplar_set(self, z_mean, z_log_var, dataset, cache, x_indices):
         if self.args.approximate_prior is False:
-            override = getattr(self, '_exemplar_indices_override', None)
-            if isinstance(override, tuple):
+            h = handoff.current()
+            if h is not None and h.rows is not None:
                 # graph-captured step (evae/graph.py): this rank's indices already sit in a static device buffer
-                rows_ext, n_local = override
-                local = rows_ext[:n_local]
+                local = h.rows[:h.n_rows]
                 centres, logvar = self.q_z(self._exemplar_store(dataset), prior=True, rows=local)
-                dd = getattr(self, '_exemplar_dedup', None)
+                dd = h.dedup
                 if dd is not None:
                     # the gather list holds the DISTINCT rows of the draw (evae/graph.py; of this rank's slice of it when
                     # sharded): the prior gets every draw's encoding, log-variance and index -- what the reference's
@@ -600,9 +592,10 @@ class BaseModel(nn.Module, ABC):
         data-dependent `unique`: every slot is re-encoded, the repeats of a position carry c_idx = PRIOR_MASK_ALL, which the
         prior kernels exclude from the mixture and count like leave-one-out hits -- so the denominator is #unique - #hits as
         in the reference, while every shape is static and the whole step can be captured into a hipGraph."""
-        override = getattr(self, '_exemplar_indices_override', None)
-        if isinstance(override, tuple):          # captured step: the candidate draw already sits in a static device buffer
-            exemplars_indices = override[0][:override[1]]
+        h = handoff.current()
+        captured = h is not None and h.rows is not None
+        if captured:                             # captured step: the candidate draw already sits in a static device buffer
+            exemplars_indices = h.rows[:h.n_rows]
         else:
             exemplars_indices = self._indices_to_device(torch.randint(low=0, high=self.args.training_set_size,
                                                                       size=(self.args.number_components,)))
@@ -621,11 +614,11 @@ class BaseModel(nn.Module, ABC):
             nearest_indices, _ = ops.pairdist_topk(z.detach(), sub_cache.detach(), self.args.approximate_k, want_val=False)
             # static slots: always for the dense encoders (a repeated slot costs one thin GEMM row), for the convolutional
             # ones only inside a captured step -- re-encoding up to B * k images where `unique` leaves a few dozen is not free
-            static = self.args.no_mask is False and (not self._is_conv() or isinstance(override, tuple))
+            static = self.args.no_mask is False and (not self._is_conv() or captured)
             if static and nearest_indices.numel() > ops.SELECT_EXEMPLARS_MAX:
                 # evae_select_exemplars keeps all B * k positions of a call in one block's LDS: beyond its limit the
                 # data-dependent `unique` form below takes over (not capturable: a captured step refuses this size up front)
-                if isinstance(override, tuple):
+                if captured:
                     raise RuntimeError("approximate prior: batch_size * approximate_k = %d exceeds the %d static slots a "
                                        "captured step supports; run with use_hip_graph=False"
                                        % (nearest_indices.numel(), ops.SELECT_EXEMPLARS_MAX))

@@ -356,3 +356,39 @@ def test_bench_dump_outputs_types_budget_and_sample(tmp_path, monkeypatch):
     a1, a2 = np.load(tmp_path / "b1" / "a.npy"), np.load(tmp_path / "b2" / "a.npy")
     assert a1.size < 300000 and np.array_equal(a1, a2) and np.isin(a1, big["a"].numpy()).all()
     assert np.array_equal(np.load(tmp_path / "b1" / "b.npy"), big["b"].numpy())
+
+
+def test_step_handoff_scope_and_take_once_tokens():
+    """evae/handoff.py alone: one slot; a block restores the hand-off before it, exception or not; a head-launch token is
+    honoured once and only for the pointers it was recorded for; no token outlives its block."""
+    from evae import handoff
+    assert handoff.current() is None
+    outer, inner = handoff.StepHandoff("rows", 3, "tables"), handoff.StepHandoff()
+    assert (outer.rows, outer.n_rows, outer.dedup, outer.eps, outer.batch_staged, outer.unit_upstream, outer.beta) == \
+        ("rows", 3, "tables", None, False, False, None)
+    with handoff.active(outer) as h:
+        assert h is outer and handoff.current() is outer
+        with handoff.active(inner):
+            assert handoff.current() is inner
+        assert handoff.current() is outer                          # nesting restores the outer object
+        with pytest.raises(KeyError):
+            with handoff.active(inner):
+                raise KeyError("inside")
+        assert handoff.current() is outer                          # ... and so does an exception
+        # taken once
+        outer.prep, outer.wt, outer.p6 = (1, 2, 3), ((4, 5, 6), "bufs"), (7, 8)
+        assert outer.take_prep(1, 2, 3) is True and outer.take_prep(1, 2, 3) is False
+        assert outer.take_wt(4, 5, 6) == "bufs" and outer.take_wt(4, 5, 6) is None
+        assert outer.take_p6(7, 8) is True and outer.take_p6(7, 8) is False
+        # other pointers: refused, and refused from then on (the right ones included)
+        outer.prep, outer.wt, outer.p6 = (1, 2, 3), ((4, 5, 6), "bufs"), (7, 8)
+        assert outer.take_prep(1, 2, 9) is False and outer.take_prep(1, 2, 3) is False
+        assert outer.take_wt(4, 9, 6) is None and outer.take_wt(4, 5, 6) is None
+        assert outer.take_p6(9, 8) is False and outer.take_p6(7, 8) is False
+        outer.prep, outer.wt, outer.p6 = (1, 2, 3), ((4, 5, 6), "bufs"), (7, 8)      # never taken
+        outer.p6_images = "images"
+    assert handoff.current() is None                               # nothing is active after the block
+    assert (outer.prep, outer.wt, outer.p6) == (None, None, None)  # and no token survived it
+    assert outer.p6_images == "images"                             # (the report to the runner did)
+    with pytest.raises(AttributeError):
+        outer.no_such_field = 1                                    # named fields only
