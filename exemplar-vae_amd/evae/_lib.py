@@ -82,6 +82,12 @@ SIGNATURES = {
     "evae_prior_lse_bwd_workspace_bytes": (_z, [_i, _i, _i]),
     "evae_prior_lse_bwd": (_i, [_p, _i, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _z, _p]),
     "evae_prior_lse_bwd_phased": (_i, [_p, _i, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _z, _i, _p]),
+    "evae_mixture_lse_fwd_workspace_bytes": (_z, [_i, _i, _i]),
+    "evae_mixture_lse_fwd": (_i, [_p, _i, _p, _p, _i, _i, _f, _p, _p, _p, _p, _z, _p]),
+    "evae_mixture_lse_bwd_workspace_bytes": (_z, [_i, _i, _i]),
+    "evae_mixture_lse_bwd": (_i, [_p, _i, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _z, _p]),
+    "evae_pseudo_inputs_fwd": (_i, [_p, _i, _i, _p, _p]),
+    "evae_pseudo_inputs_bwd": (_i, [_p, _p, _i, _i, _p, _p]),
     "evae_pairdist_topk_workspace_bytes": (_z, [_i, _i, _i, _i]),
     "evae_pairdist_topk": (_i, [_p, _i, _p, _i, _i, _i, _u, _l, _p, _p, _p, _z, _p]),
     "evae_pairwise_distance": (_i, [_p, _i, _p, _i, _i, _p, _p]),

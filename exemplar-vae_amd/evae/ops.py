@@ -375,6 +375,110 @@ def prior_logp(z, centres, log_var_row, z_idx, c_idx):
 
 
 # ------------------------------------------------------------------------------------------------
+# VampPrior: mixture of diagonal Gaussians with per-component variance (csrc/evae_mixture.hip)
+# ------------------------------------------------------------------------------------------------
+def _mixture_args(z, means, log_var):
+    _need_cuda(z, means, log_var)
+    z, means, log_var = _f32(z), _f32(means), _f32(log_var)
+    if z.dim() != 2 or means.dim() != 2 or means.shape != log_var.shape or means.shape[1] != z.shape[1]:
+        raise _lib.EvaeError("mixture: z [B x zdim], means and log_var [C x zdim] expected, got %s, %s, %s"
+                             % (tuple(z.shape), tuple(means.shape), tuple(log_var.shape)))
+    return z, means, log_var
+
+
+def mixture_lse_fwd(z, means, log_var, n_components, want_prob=False):
+    """log p(z_i) under the uniform mixture of the C diagonal Gaussians (means_j, exp(log_var_j)), weight 1 / n_components each:
+    (logp [B], token [2 x B] for mixture_lse_bwd, prob [B x C] or None)."""
+    lib = _lib.load()
+    z, means, log_var = _mixture_args(z, means, log_var)
+    B, zd = z.shape
+    Cn = means.shape[0]
+    logp = torch.empty(B, device=z.device)
+    token = torch.empty((2, B), device=z.device)
+    prob = torch.empty((B, Cn), device=z.device) if want_prob else None
+    ws = _workspace("mixture_fwd", lib.evae_mixture_lse_fwd_workspace_bytes(B, Cn, zd), z.device)
+    _lib.check(lib.evae_mixture_lse_fwd(_p(z), B, _p(means), _p(log_var), Cn, zd, float(n_components), _p(logp), _p(token),
+                                        _p(prob), _p(ws), ws.numel(), _stream()), "evae_mixture_lse_fwd")
+    return logp, token, prob
+
+
+def mixture_lse_bwd(z, means, log_var, n_components, lse, grad_out, need=(True, True, True)):
+    """Gradients (dz, dmeans, dlog_var) of sum_i grad_out_i logp_i from the token of mixture_lse_fwd; `need` leaves out the
+    ones nobody asked for (None in their place).  n_components only shifts logp: it does not enter the gradients."""
+    lib = _lib.load()
+    z, means, log_var = _mixture_args(z, means, log_var)
+    _need_cuda(lse, grad_out)
+    lse, grad_out = _f32(lse), _f32(grad_out).reshape(-1)
+    B, zd = z.shape
+    Cn = means.shape[0]
+    assert lse.numel() == 2 * B and grad_out.numel() == B, "mixture_lse_bwd: lse is the [2 x B] token of mixture_lse_fwd"
+    dz = torch.empty_like(z) if need[0] else None
+    dm = torch.empty_like(means) if need[1] else None
+    dlv = torch.empty_like(log_var) if need[2] else None
+    ws = _workspace("mixture_bwd", lib.evae_mixture_lse_bwd_workspace_bytes(B, Cn, zd), z.device)
+    _lib.check(lib.evae_mixture_lse_bwd(_p(z), B, _p(means), _p(log_var), Cn, zd, _p(lse), _p(grad_out), _p(dz), _p(dm), _p(dlv),
+                                        _p(ws), ws.numel(), _stream()), "evae_mixture_lse_bwd")
+    return dz, dm, dlv
+
+
+class MixtureLogP(torch.autograd.Function):
+    """log p(z_i) under the VampPrior mixture (models/BaseModel.py:84-96,124-128).
+    forward(z, means [C x zdim], log_var [C x zdim], n_components) -> logp [B]."""
+
+    @staticmethod
+    def forward(ctx, z, means, log_var, n_components):
+        logp, token, _ = mixture_lse_fwd(z, means, log_var, n_components)
+        ctx.save_for_backward(z, means, log_var, token)
+        ctx.n_components = n_components
+        return logp
+
+    @staticmethod
+    def backward(ctx, g):
+        z, means, log_var, token = ctx.saved_tensors
+        need = tuple(ctx.needs_input_grad[:3])
+        dz, dm, dlv = mixture_lse_bwd(z, means, log_var, ctx.n_components, token, g, need=need)
+        return dz, dm, dlv, None
+
+
+def mixture_logp(z, means, log_var, n_components):
+    """log p(z) [B] under the VampPrior mixture, differentiable in z, means and log_var"""
+    _need_cuda(z, means, log_var)
+    return MixtureLogP.apply(z, means, log_var, float(n_components))
+
+
+class PseudoInputsFn(torch.autograd.Function):
+    """X [C x D] = clamp(W^T, 0, 1) for the [D x C] weight of the VampPrior's `means` layer: what hardtanh(eye(C) @ W^T) gives,
+    without the identity GEMM forward and its weight-gradient GEMM backward."""
+
+    @staticmethod
+    def forward(ctx, weight):
+        lib = _lib.load()
+        w = _f32(weight)
+        D, Cn = w.shape
+        out = torch.empty((Cn, D), device=w.device)
+        _lib.check(lib.evae_pseudo_inputs_fwd(_p(w), D, Cn, _p(out), _stream()), "evae_pseudo_inputs_fwd")
+        ctx.save_for_backward(w)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        w, = ctx.saved_tensors
+        D, Cn = w.shape
+        g = _f32(g)
+        dw = torch.empty_like(w)
+        _lib.check(lib.evae_pseudo_inputs_bwd(_p(w), _p(g), D, Cn, _p(dw), _stream()), "evae_pseudo_inputs_bwd")
+        return dw
+
+
+def pseudo_inputs(weight):
+    _need_cuda(weight)
+    if weight.dim() != 2:
+        raise _lib.EvaeError("pseudo_inputs: a [D x C] weight expected, got %s" % (tuple(weight.shape),))
+    return PseudoInputsFn.apply(weight)
+
+
+# ------------------------------------------------------------------------------------------------
 # distance + top-K
 # ------------------------------------------------------------------------------------------------
 def pairdist_topk(q, cache, k, sqrt=False, index_base=0, want_val=True):

@@ -11,8 +11,11 @@ MI355X kernels of libevae_hip.so (evae.ops).  What changed underneath, not in be
 * with torch.distributed initialised and args.shard_exemplars=True, the exemplar set is sharded across
   ranks and the per-shard partial log-sum-exps are merged after one RCCL all-gather (evae.shard).
 
-Out of scope: the vampprior branch and the image-generation helpers keep their
-names and run on plain torch ops."""
+* the VampPrior (--prior vampprior) scores z against its per-component-variance mixture in one fused kernel
+  (evae.ops.MixtureLogP, csrc/evae_mixture.hip) and reads its pseudo-inputs as a transposing clamp of the `means` weight
+  (pseudo_inputs()) in place of the identity GEMM; its training step stays eager and unsharded.
+
+Out of scope: the image-generation helpers keep their names and run on plain torch ops."""
 import math
 import os
 from abc import ABC, abstractmethod
@@ -210,13 +213,26 @@ class BaseModel(nn.Module, ABC):
         return z
 
     # ------------------------------------------------------------------ priors
-    def log_p_z_vampprior(self, z, exemplars_embedding):
+    def pseudo_inputs(self):
+        """The VampPrior's pseudo-inputs [C x D] (reference :130-140: self.means(self.idle_input), the identity pushed through a
+        bias-free hardtanh layer).  On the GPU: clamp(W^T, 0, 1) by one transposing kernel, the same bits without the GEMMs."""
+        w = self.means.linear.weight
+        if w.is_cuda:
+            return ops.pseudo_inputs(w)
+        return self.means(self.idle_input)
+
+    def _vampprior_components(self, exemplars_embedding):
         if exemplars_embedding is None:
-            C = self.args.number_components
-            z_p_mean, z_p_logvar = self.q_z(self.means(self.idle_input), prior=True)
-        else:
-            C = self.args.number_components
-            z_p_mean, z_p_logvar = exemplars_embedding
+            return self.q_z(self.pseudo_inputs(), prior=True)
+        return exemplars_embedding
+
+    def log_p_z_vampprior(self, z, exemplars_embedding):
+        """[B x C] matrix log N(z_i | mu_j, exp(lv_j)) - log(number_components) (reference :84-96).  Differentiable like the
+        reference's: with a gradient requested it is the torch composition, otherwise one pass of the fused kernel."""
+        C = self.args.number_components
+        z_p_mean, z_p_logvar = self._vampprior_components(exemplars_embedding)
+        if z.is_cuda and not (torch.is_grad_enabled() and (z.requires_grad or z_p_mean.requires_grad or z_p_logvar.requires_grad)):
+            return ops.mixture_lse_fwd(z, z_p_mean, z_p_logvar, C, want_prob=True)[2]
         return log_normal_diag(z.unsqueeze(1), z_p_mean.unsqueeze(0), z_p_logvar.unsqueeze(0), dim=2) - math.log(C)
 
     def _sharded(self):
@@ -252,6 +268,9 @@ class BaseModel(nn.Module, ABC):
         if self.args.prior == 'standard':
             return log_normal_standard(z, dim=1)
         if self.args.prior == 'vampprior':
+            if sum and z.is_cuda:
+                z_p_mean, z_p_logvar = self._vampprior_components(exemplars_embedding)
+                return ops.mixture_logp(z, z_p_mean, z_p_logvar, self.args.number_components)
             prob = self.log_p_z_vampprior(z, exemplars_embedding)
             if not sum:
                 return prob
@@ -303,7 +322,7 @@ class BaseModel(nn.Module, ABC):
         if self.args.prior == 'standard':
             return torch.randn(N, self.args.z1_size, device=self.args.device)
         if self.args.prior == 'vampprior':
-            means = self.means(self.idle_input)[0:N]
+            means = self.pseudo_inputs()[0:N]
             mu, logvar = self.q_z(means)
             return self.reparameterize(mu, logvar)
         rand_indices = torch.randint(low=0, high=self.args.training_set_size, size=(N,))

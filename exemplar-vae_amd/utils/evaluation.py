@@ -24,7 +24,7 @@ def load_all_pseudo_input(args, model, dataset):
         exemplars_z, exemplars_log_var = model.cache_z(dataset)
         return (exemplars_z, exemplars_log_var, torch.arange(len(exemplars_z)))
     if args.prior == 'vampprior':
-        pseudo_means = model.means(model.idle_input)
+        pseudo_means = model.pseudo_inputs()
         if 'conv' in args.model_name:
             pseudo_means = pseudo_means.view(-1, args.input_size[0], args.input_size[1], args.input_size[2])
         return model.q_z(pseudo_means, prior=True)

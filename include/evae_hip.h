@@ -183,6 +183,50 @@ int evae_prior_lse_bwd_phased(const float* z, int B, const float* centres, int C
                               evae_stream_t stream);
 
 /* ----------------------------------------------------------------------------------------------
+ * VampPrior: a uniform mixture of diagonal Gaussians whose components each carry their OWN mean and log-variance.
+ * Replaces models/BaseModel.py:84-96 (log_p_z_vampprior) and the max / log-sum-exp of :124-128 without materialising
+ * the [B x C x zdim] difference tensor (csrc/evae_mixture.hip).
+ *
+ *   p_ij   = -1/2 sum_d [ lv_jd + log 2pi + (z_id - mu_jd)^2 exp(-lv_jd) ] - log(n_components)
+ *   logp_i = max_j p_ij + log sum_j exp(p_ij - max_j p_ij)
+ *
+ * n_components is the model's number_components (reference :86,:89), NOT C: with an embedding passed in the two can differ.
+ * Direct differences on the VALU for every zdim (1 <= zdim <= 512; B, C >= 1): with lv down to -6, exp(-lv) reaches 403 and
+ * the expanded form z^2 w - 2 z mu w + mu^2 w cancels in fp32.  exp(-lv) is taken once per component element.
+ * evae_mixture_lse_fwd writes out_logp [B], the forward -> backward token out_lse [2 B] of evae_prior_merge (row maximum and
+ * log of the normalised sum of the p_ij BEFORE the - log(n_components); NULL: not wanted) and, when out_prob != NULL, the
+ * matrix p_ij [B x C] (log_p_z(sum=False)).  The component range is split over blocks when there are few queries; the
+ * per-split (max, sumexp) partials are three planes of nsplit x B floats in the workspace (the third, the masked count, is 0),
+ * merged in split order by evae_prior_merge(nmask = 0, c_total = n_components).
+ * The result depends on (B, C, zdim) and the data only: two calls on the same inputs return the same bits.
+ */
+size_t evae_mixture_lse_fwd_workspace_bytes(int B, int C, int zdim);
+int evae_mixture_lse_fwd(const float* z /* [B x zdim] */, int B, const float* means /* [C x zdim] */,
+                         const float* log_var /* [C x zdim] */, int C, int zdim, float n_components,
+                         float* out_logp /* [B] */, float* out_lse /* token [2 B] or NULL */,
+                         float* out_prob /* [B x C] or NULL */, void* ws, size_t ws_bytes, evae_stream_t stream);
+/* Backward of sum_i grad_out_i * logp_i by recomputation from the token (p_ij is formed exactly as in the forward):
+ *   r_ij = grad_out_i exp(p_ij - lse_i);  w_jd = exp(-lv_jd)
+ *   dz_i   = sum_j r_ij (mu_j - z_i) w_j
+ *   dmu_j  = sum_i r_ij (z_i - mu_j) w_j
+ *   dlv_jd = sum_i r_ij 1/2 ((z_id - mu_jd)^2 w_jd - 1)
+ * dz, dmeans, dlog_var may each be NULL (not wanted: the launch that only serves it is skipped).  dmeans / dlog_var are
+ * finished by the wave that owns the component, walking the queries in order; dz is summed over the component splits in
+ * split order.  No floating-point atomics: bit-identical from run to run.  ws is only read when dz != NULL. */
+size_t evae_mixture_lse_bwd_workspace_bytes(int B, int C, int zdim);
+int evae_mixture_lse_bwd(const float* z, int B, const float* means, const float* log_var, int C, int zdim,
+                         const float* lse /* token [2 B] of evae_mixture_lse_fwd */, const float* grad_out /* [B] */,
+                         float* dz /* [B x zdim] or NULL */, float* dmeans /* [C x zdim] or NULL */,
+                         float* dlog_var /* [C x zdim] or NULL */, void* ws, size_t ws_bytes, evae_stream_t stream);
+/* The VampPrior's pseudo-inputs (models/BaseModel.py:130-140: hardtanh_[0,1](idle_input @ W^T) with idle_input the identity):
+ *   out[c, d] = min(max(weight[d, c], 0), 1)           weight [D x C] = means.linear.weight, out [C x D]
+ *   dweight[d, c] = dout[c, d] where 0 < weight[d, c] < 1, else 0      (hardtanh's backward, strict inequalities)
+ * a transposing copy through LDS; bit-equal to the identity GEMM (one non-zero product per output). */
+int evae_pseudo_inputs_fwd(const float* weight /* [D x C] */, int D, int C, float* out /* [C x D] */, evae_stream_t stream);
+int evae_pseudo_inputs_bwd(const float* weight /* [D x C] */, const float* dout /* [C x D] */, int D, int C,
+                           float* dweight /* [D x C] */, evae_stream_t stream);
+
+/* ----------------------------------------------------------------------------------------------
  * Distance + top-K.  Replaces pairwise_distance(z, sub_cache).topk(k, largest=False)
  * (models/BaseModel.py:263-264) and find_nearest_neighbors (utils/knn_on_latent.py:4-9: sqrt of the
  * direct-difference distance, topk(k=20, sorted=True)).

@@ -844,7 +844,67 @@ def g18():
     print("g18_state_dict_shapes.json %.1f KB, %d architectures" % (os.path.getsize(path) / 1024, len(out)))
 
 
+# ---- G24: the VampPrior mixture (models/BaseModel.py:84-96,124-128) at function level and through vae / hvae_2level ----
+G24 = dict(B=37, C=301, zdim=40, seed=241, model_C=77, model_B=16, model_D=64, model_z=8)
+
+
+def g24():
+    import vampprior_ref as vr
+    from models.HVAE_2level import VAE as HVAE
+    from utils.evaluation import evaluate_loss
+    out = {}
+    # (a) function level: log_p_z with an embedding of 301 components, per-component variances, number_components = 301
+    B, C, zdim = G24["B"], G24["C"], G24["zdim"]
+    z_np, mu_np, lv_np, gout = vr.inputs(G24["seed"], B, C, zdim)
+    args = vae_args(prior="vampprior", input_size=[1, 8, 8], hidden_size=32, z1_size=zdim, z2_size=zdim, number_components=C,
+                    training_set_size=100)
+    args.pseudoinputs_mean, args.pseudoinputs_std, args.use_training_data_init = 0.05, 0.01, False
+    torch.manual_seed(240)
+    model = VAE(args)
+    # The reference's code is handed the fp32 inputs as float64 tensors, so that what is stored is its formula and not its fp32
+    # rounding: with lv down to -6 the p_ij reach thousands, and fp32 softmax weights carry ~2e-6 of the gradients' magnitude --
+    # more than the 1e-6 the fp64 restatement (tests/vampprior_ref.py) is held to.  Stored rounded to fp32 (6e-8 relative).
+    z, mu, lv = (T(a).double().requires_grad_(True) for a in (z_np, mu_np, lv_np))
+    logp = model.log_p_z((z, None), (mu, lv), sum=True)
+    (logp * T(gout).double()).sum().backward()
+    with torch.no_grad():
+        prob = model.log_p_z((T(z_np).double(), None), (T(mu_np).double(), T(lv_np).double()), sum=False)
+    assert logp.dtype == torch.float64 and prob.dtype == torch.float64 and z.grad.dtype == torch.float64
+    f32 = lambda t: t.detach().numpy().astype(np.float32)
+    out.update(a_z=z_np, a_mu=mu_np, a_lv=lv_np, a_gout=gout, a_logp=f32(logp), a_prob=f32(prob),
+               a_dz=f32(z.grad), a_dmu=f32(mu.grad), a_dlv=f32(lv.grad))
+    # (b) model level, as G15: 77 pseudo-inputs (odd, more than one wave of components, fewer than two)
+    Bm, D, Cm, zm = G24["model_B"], G24["model_D"], G24["model_C"], G24["model_z"]
+    x = gi.binary_images(242, Bm, D)
+    test = gi.binary_images(243, 24, D)
+    eps = np.random.RandomState(244).standard_normal((Bm, zm)).astype(np.float32)
+    out["eps"] = eps
+    for tag, cls in (("vae", VAE), ("hvae_2level", HVAE)):
+        args = vae_args(prior="vampprior", model_name=tag, input_size=[1, 8, 8], hidden_size=32, z1_size=zm, z2_size=zm,
+                        number_components=Cm, training_set_size=100)
+        args.pseudoinputs_mean, args.pseudoinputs_std, args.use_training_data_init = 0.05, 0.01, False
+        args.batch_size = Bm
+        torch.manual_seed(245)
+        model = cls(args)
+        model.train()
+        for k, v in model.state_dict().items():
+            out[tag + "_sd_" + k] = v.numpy().copy()
+        model.reparameterize = lambda mu, logvar: T(eps[:mu.shape[0]]) * logvar.mul(0.5).exp() + mu
+        loss, RE, KL = model.calculate_loss((T(x), torch.arange(Bm).reshape(-1, 1)), 0.7, average=False)
+        loss.mean().backward()
+        out[tag + "_loss"], out[tag + "_RE"], out[tag + "_KL"] = (t.detach().numpy() for t in (loss, RE, KL))
+        for n, p_ in model.named_parameters():
+            out[tag + "_gnorm_" + n] = np.asarray(0.0 if p_.grad is None else p_.grad.double().norm().item())
+        out[tag + "_grad_means.linear.weight"] = model.means.linear.weight.grad.numpy().copy()
+        model.eval()
+        model.reparameterize = lambda mu, logvar: mu
+        loader = torch.utils.data.DataLoader(torch.utils.data.TensorDataset(T(test), torch.zeros(24)), batch_size=8)
+        with torch.no_grad():
+            out[tag + "_eval"] = np.asarray(evaluate_loss(args, model, loader, dataset=None))
+    save("g24_vampprior", **out)
+
+
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["g1_g2", "g3", "g4", "g5", "g6", "g6_conv", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16", "g17", "g18", "g19", "g20", "g21", "g22", "g23"]
+    which = sys.argv[1:] or ["g1_g2", "g3", "g4", "g5", "g6", "g6_conv", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16", "g17", "g18", "g19", "g20", "g21", "g22", "g23", "g24"]
     for w in which:
         globals()[w]()
