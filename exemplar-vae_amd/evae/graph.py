@@ -16,6 +16,11 @@ counter-based generator (evae_batch_prologue: seed = torch's seed when the runne
 in the control block); whatever else draws random numbers uses the CUDA generator, which torch registers with the
 capture so that every replay advances its Philox offset.  RCCL collectives of the sharded prior are captured too.
 
+A VampPrior step (utils/training.py::vampprior_step_eligible) runs through the same runner with NO exemplar rows: the control
+block is [staging rows | batch indices | seed, counter | beta, step sizes], _refresh draws nothing, and the model's modular
+autograd path is what gets captured; the prologue's eps serves the `vae` model (models/BaseModel.py::_draw_eps), the prior is
+ops.MixtureLogP's launches, the ones an eager step issues.
+
 What the model and the fused node have to know about the step that is running -- its gather list, the distinct-row tables, the
 prologue's eps, the promise that the only backward is loss.backward(ones), what the head launch already did for them -- travels
 on ONE object, evae/handoff.py's StepHandoff: _step_scope installs it for the length of a call and takes it away again, so
@@ -61,7 +66,11 @@ class GraphedTrainStep:
         self.binarize = bool(dynamic_binarization)
         dev = torch.device(a.device)
         D = int(torch.tensor(a.input_size).prod().item())
-        C = int(a.number_components)
+        # a prior without exemplar rows (the VampPrior: its components are the model's own pseudo-inputs, and number_components is
+        # NOT a number of dataset rows) has an empty head in the gather list: no draw, no distinct-row tables, nothing of the
+        # dataset is indexed with number_components
+        self.no_exemplars = a.prior != 'exemplar_prior'
+        C = 0 if self.no_exemplars else int(a.number_components)
         self.x_in = torch.zeros((self.B, D), device=dev)
         # gather list of the fused step: [this rank's exemplar indices | the staging rows of the batch]; only the head
         # changes between steps, so the captured graph needs no arange/cat
@@ -199,6 +208,7 @@ class GraphedTrainStep:
         self.eager_opt = False     # True: the participants' step counts differ (resumed checkpoint): eager optimizer steps only
         self.warmup_steps = max(2, warmup_steps)    # call 0 learns the optimizer's participants, call 1 warms the captured form
         self._calls = 0
+        self.replays = 0           # steps that were replays of the captured graph
 
     def reset_totals(self):
         self.totals.zero_()
@@ -333,7 +343,9 @@ class GraphedTrainStep:
         if T: t0 = T.lap("wait for the block's last upload", t0)
         h = self._h_ctl[k]
         # same CPU-generator draw, with replacement, as the reference (models/BaseModel.py:245)
-        if self.dedup is not None:
+        if self.no_exemplars:
+            pass                                  # (no exemplar rows: the CPU generator is left alone, as in the reference's step)
+        elif self.dedup is not None:
             dr = h[self._o_draw:self._o_inv]
             if Cl == a.number_components:
                 torch.randint(low=0, high=a.training_set_size, size=(Cl,), out=dr)
@@ -496,6 +508,7 @@ class GraphedTrainStep:
                     return self.out
                 # capture does not execute: replay once for this call's step
             self.graph.replay()
+            self.replays += 1
             self._calls += 1
             if shard.is_active() and self._calls % shard.REPLICA_CHECK_EVERY == 0:
                 shard.check_replicas(self.model.parameters())      # (replica mode's guard: raises when the ranks drifted apart)

@@ -13,7 +13,9 @@ MI355X kernels of libevae_hip.so (evae.ops).  What changed underneath, not in be
 
 * the VampPrior (--prior vampprior) scores z against its per-component-variance mixture in one fused kernel
   (evae.ops.MixtureLogP, csrc/evae_mixture.hip) and reads its pseudo-inputs as a transposing clamp of the `means` weight
-  (pseudo_inputs()) in place of the identity GEMM; its training step stays eager and unsharded.
+  (pseudo_inputs()) in place of the identity GEMM; the training step of `vae` / `hvae_2level` replays from one hipGraph
+  (utils/training.py::vampprior_step_eligible), the same launches as the eager step;
+  the convolutional models' step stays eager, and nothing of it is sharded.
 
 Out of scope: the image-generation helpers keep their names and run on plain torch ops."""
 import math
@@ -203,6 +205,12 @@ class BaseModel(nn.Module, ABC):
     def _draw_eps(self, like):
         """Standard-normal noise from the device generator (reference :81); tests override this to inject
         identical eps into the reference, the oracle and this model."""
+        h = handoff.current()
+        if (h is not None and h.eps is not None and self.args.prior == 'vampprior' and self.args.model_name == 'vae'
+                and self.training and tuple(h.eps.shape) == tuple(like.shape)):
+            # a captured VampPrior step of `vae`, the one model with ONE draw per step: the noise its prologue launch drew
+            # (evae/graph.py).  hvae_2level draws z2 and z1 with the same shape and must not get one buffer twice
+            return h.eps
         g = getattr(self, '_eps_generator', None)      # evaluation over a sharded cache: the same stream on every rank (evae/shard.py)
         if g is not None:
             return torch.randn(like.shape, generator=g, device=like.device, dtype=like.dtype)

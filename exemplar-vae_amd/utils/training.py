@@ -60,9 +60,20 @@ def train_one_epoch(epoch, args, train_loader, model, optimizer):
     return train_loss, train_re, train_kl
 
 
+def vampprior_step_eligible(a):
+    """Whether a VampPrior training step of the configuration `a` is captured -- a function of the arguments alone: the dense
+    models (`vae`, `hvae_2level`) on one device.  The convolutional models stay eager (their step is not bound by the host, and
+    their captured form has not been validated with this prior), and so does any configuration that asks for sharding
+    (shard_exemplars: the pseudo-inputs are parameters of every rank, there is nothing to shard)."""
+    return (a.prior == 'vampprior' and a.model_name in ('vae', 'hvae_2level')
+            and not bool(getattr(a, 'shard_exemplars', False)))
+
+
 def _graphed_step(args, model, optimizer, train_loader):
     """The captured-step runner for this (model, optimizer, dataset), or None when the configuration is not
-    the graph-capturable one (fused `vae` exact-prior path on a GPU) or args.use_hip_graph is False."""
+    a graph-capturable one or args.use_hip_graph is False.  Capturable: the exemplar prior (below), and the VampPrior of the
+    dense models on one device (vampprior_step_eligible; convolutional models, and every process of a torch.distributed group
+    of several ranks, step eagerly) -- its step runs the modular autograd path with no exemplar rows in the runner (evae/graph.py)."""
     if not getattr(args, 'use_hip_graph', True) or not str(args.device).startswith('cuda'):
         return None
     a = model.args
@@ -73,6 +84,8 @@ def _graphed_step(args, model, optimizer, train_loader):
     # the graph (exact prior), every other case its modular autograd path
     ok = a.prior == 'exemplar_prior' and (a.approximate_prior is False or
                                           (a.no_mask is False and not model._sharded() and not model._is_conv()))
+    if a.prior == 'vampprior':
+        ok = vampprior_step_eligible(a) and not shard.is_active()      # one device: no torch.distributed group of several ranks
     if not ok:
         return None
     # the runner keeps the optimizer and the dataset alive, so their ids cannot be recycled while it is cached
