@@ -84,13 +84,7 @@ __global__ __launch_bounds__(64 * NW, NW / 2) void conv_gemm_kernel(const ConvAr
   auto Bs = [&](int b) -> float* { return smem + b * STAGE + A_TILE_FLOATS; };
   const ConvGeom& g = a.g;
 
-  const int ntiles = a.tiles_m * a.tiles_n;
-  int tile;
-  {
-    const int id = blockIdx.x, xcd = id & 7, slot = id >> 3;
-    const int qq = ntiles >> 3, rr = ntiles & 7;
-    tile = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + slot;
-  }
+  const int tile = tile_of_block(blockIdx.x, a.tiles_m * a.tiles_n);
   const int tm = tile / a.tiles_n, tn = tile - tm * a.tiles_n;
   const int m0 = tm * BM;
   const int n0 = GATED ? tn * 64 : tn * BN_;
@@ -491,7 +485,7 @@ static int launch_conv(ConvArgs& a, int nz, hipStream_t stream, const char* what
   }
   a.tiles_m = cdiv(a.M, BM);
   a.tiles_n = cdiv(a.Ncols, EPI == CEPI_GATED ? 64 : BN_);
-  conv_gemm_kernel<MODE, EPI, BN_, 8><<<dim3(a.tiles_m * a.tiles_n, 1, nz), 512, lds, stream>>>(a);
+  conv_gemm_kernel<MODE, EPI, BN_, 8><<<dim3(tile_grid(a.tiles_m * a.tiles_n), 1, nz), 512, lds, stream>>>(a);
   return check_launch(what);
 }
 

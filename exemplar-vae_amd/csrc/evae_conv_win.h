@@ -532,14 +532,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   __builtin_assume(wave >= 0 && wave < 4);
   const int wr = wave / WC, wc = wave - wr * WC, l31 = lane & 31, lh = lane >> 5;
-  // XCD-aware tile order: XCD x (= block id mod 8) works on a contiguous run of tiles (neighbouring windows share halo rows)
-  const int ntiles = gridDim.x;
-  int tile;
-  {
-    const int id = blockIdx.x, xcd = id & 7, slot = id >> 3;
-    const int qq = ntiles >> 3, rr = ntiles & 7;
-    tile = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + slot;
-  }
+  const int tile = tile_of_block(blockIdx.x, gridDim.x);       // neighbouring windows share halo rows
   const int tm = tile / g.tiles_n, tn = tile - tm * g.tiles_n;
   const int m0 = tm * R;
   const int HW = g.H * g.W;
@@ -604,14 +597,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
   };
 
-  p6_bf16x8 af[2][MT][3], bf[2][NT][3];
+  bf16x8 af[2][MT][3], bf[2][NT][3];
   auto read_a = [&](auto par_, unsigned ab, int mt, int p) {
     constexpr int par = decltype(par_)::value;
-    af[par][mt][p] = *reinterpret_cast<const p6_bf16x8*>(lds + ab + p * WP);
+    af[par][mt][p] = *reinterpret_cast<const bf16x8*>(lds + ab + p * WP);
   };
   auto read_b = [&](auto par_, int buf, int kk, int nt, int p) {
     constexpr int par = decltype(par_)::value;
-    bf[par][nt][p] = *reinterpret_cast<const p6_bf16x8*>(lds + fb[nt] + buf * BST + kk * BKS + p * (BN * 32));
+    bf[par][nt][p] = *reinterpret_cast<const bf16x8*>(lds + fb[nt] + buf * BST + kk * BKS + p * (BN * 32));
   };
   // window byte address of this lane's fragment of row tile mt at tap offset `to` (slots)
   auto a_addr = [&](int mt, int to) -> unsigned {
@@ -803,7 +796,7 @@ static int launch_conv_win(ConvWinArgs& g, hipStream_t stream, const char* what)
   const int tiles_m = cdiv(g.M, G::R);
   if (g.stagger == 0 && tiles_m * g.tiles_n > 640) { const int u = g.nks_w / 8; g.stagger = u < 1 ? 1 : (u > 8 ? 8 : u); }
   if (g.stagger < 0) g.stagger = 0;
-  conv_win_kernel<EPI, WR, NT, SLOTS><<<dim3(tiles_m * g.tiles_n), 256, G::lds_bytes(EPI == CW_FWD_GATED), stream>>>(g);
+  conv_win_kernel<EPI, WR, NT, SLOTS><<<tile_grid(tiles_m * g.tiles_n), 256, G::lds_bytes(EPI == CW_FWD_GATED), stream>>>(g);
   return check_launch(what);
 }
 
@@ -832,13 +825,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, lh = lane >> 5;
-  const int ntiles = gridDim.x;
-  int tile;
-  {
-    const int id = blockIdx.x, xcd = id & 7, slot = id >> 3;
-    const int qq = ntiles >> 3, rr = ntiles & 7;
-    tile = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + slot;
-  }
+  const int tile = tile_of_block(blockIdx.x, gridDim.x);
   const int tm = tile / g.tiles_n, tn = tile - tm * g.tiles_n;
   const int m0 = tm * R, HW = g.H * g.W, K = a.K, taps = K * K;
   const unsigned nf = fdiv((unsigned)m0, g.div_hw), remf = (unsigned)m0 - nf * (unsigned)HW;
@@ -926,7 +913,7 @@ static int launch_conv_first(ConvFirstArgs& a, hipStream_t stream, const char* w
   g.ostride = g.H * g.W;
   g.nat_s = 1; g.nat_h = g.H; g.nat_w = g.W; g.nat_y = g.nat_x = 0;
   g.M = g.N * g.H * g.W;
-  conv_first_kernel<SLOTS><<<dim3(cdiv(g.M, 256) * g.tiles_n), 256, LDS, stream>>>(a);
+  conv_first_kernel<SLOTS><<<tile_grid(cdiv(g.M, 256) * g.tiles_n), 256, LDS, stream>>>(a);
   return check_launch(what);
 }
 
@@ -1270,14 +1257,14 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   const unsigned one1 = l31 == 0 ? 0x3F803F80u : 0u;
   // a fragment = two transpose reads (k rows c and c + 4 -> the 8 k of this lane's row); the halves stay separate until the wait
   // for them has passed (inline-asm results are invisible to the compiler's own lgkmcnt bookkeeping)
-  struct Raw { p6_u32x2 lo, hi; };
+  struct Raw { u32x2 lo, hi; };
   auto tr2 = [&](Raw& f, unsigned a0, unsigned a1) {
     asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(f.lo) : "v"(a0));
     asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(f.hi) : "v"(a1));
   };
-  auto cook = [&](const Raw& f) -> p6_bf16x8 {
+  auto cook = [&](const Raw& f) -> bf16x8 {
     const u32x4_ v = {f.lo[0], f.lo[1], f.hi[0], f.hi[1]};
-    return __builtin_bit_cast(p6_bf16x8, v);
+    return __builtin_bit_cast(bf16x8, v);
   };
   constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};       // smallest partial products first
   // this wave's columns: tile offsets (bytes) of the real tiles; a column at or beyond NTW reads tile NTW - 1's address (and, for
@@ -1374,7 +1361,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       };
 #pragma unroll
       for (int e = 0; e < 6 + 6 * GS; ++e) read_step(0, e);
-      p6_bf16x8 af[3];
+      bf16x8 af[3];
 #pragma unroll
       for (int t = 0; t < NSTEP; ++t) {
         const int ks = t / NGRP, jg = t - ks * NGRP, j = GS * jg;
@@ -1384,7 +1371,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
           for (int p = 0; p < 3; ++p) af[p] = cook(ar[ks & 1][p]);
         }
-        p6_bf16x8 bf_[GS][3];
+        bf16x8 bf_[GS][3];
 #pragma unroll
         for (int u = 0; u < GS; ++u)
 #pragma unroll
@@ -1396,7 +1383,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
                 for (int q = 0; q < 4; ++q) v[q] = isb[j + u] ? o : v[q];
               }
-              bf_[u][p] = __builtin_bit_cast(p6_bf16x8, v);
+              bf_[u][p] = __builtin_bit_cast(bf16x8, v);
             }
         __builtin_amdgcn_sched_barrier(0);
         // 6 GS MFMAs (a wave whose row tile does not exist -- fewer than 128 merged channels -- runs the same stream on whatever its

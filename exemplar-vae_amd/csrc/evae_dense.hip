@@ -142,26 +142,9 @@ static int gated_dense_fwd_core(const float* x, const int64_t* rows, int M, int 
   g.A[0] = x; g.B[0] = wh; g.Bg = wg; g.lda[0] = ldx; g.ldb[0] = K; g.Kc[0] = K; g.npairs = 1;
   g.a_rows = rows; g.M = M; g.N = N; g.bias0 = bh; g.bias1 = bg;
   g.out0 = out; g.out1 = save_h; g.out2 = save_s; g.ldo = N; g.tsink = tsink;
-  if (pl.nz <= 1 && gemm_x6_use(g, true)) return launch_gemm_x6<EPI_GATED>(g, 1, stream, "gated_dense_fwd(x6)");
-  if (pl.nz <= 1) return launch_gemm<true, true, EPI_GATED>(g, pl, stream, "gated_dense_fwd");
-  if (ws == nullptr || ws_bytes < evae_dense_fwd_workspace_bytes(M, K, N, 1)) {
-    set_error("gated_dense_fwd: workspace too small (%zu)", ws_bytes);
-    return EVAE_EWORKSPACE;
-  }
-  g.out0 = (float*)ws; g.out1 = g.out2 = nullptr;
-  int rc;
-  if (gemm_x6_use(g, true)) {
-    g.ksplit = pl.ksplit;
-    rc = launch_gemm_x6<EPI_RAW_GATED>(g, pl.nz, stream, "gated_dense_fwd(split-K, x6)");
-  } else {
-    rc = launch_gemm<true, true, EPI_RAW_GATED>(g, pl, stream, "gated_dense_fwd(split-K)");
-  }
-  if (rc) return rc;
-  FinishArgs f = {};
-  f.ones_col = -1;
-  f.part = (const float*)ws; f.nz = pl.nz; f.M = M; f.N = N; f.ldo = N; f.epi = EPI_GATED;
-  f.bias0 = bh; f.bias1 = bg; f.out0 = out; f.out1 = save_h; f.out2 = save_s; f.tsink = tsink;
-  return launch_finish(f, stream);
+  static const GemmNames nm = {"gated_dense_fwd", "gated_dense_fwd", "gated_dense_fwd(x6)", "gated_dense_fwd(split-K)",
+                               "gated_dense_fwd(split-K, x6)"};
+  return launch_gemm_or_split<true, EPI_GATED>(g, pl, gemm_x6_use(g, true), ws, ws_bytes, stream, nm);
 }
 
 extern "C" int evae_gated_dense_fwd(const float* x, const int64_t* rows, int M, int K, int ldx,
@@ -206,27 +189,8 @@ extern "C" int evae_linear_fwd(const float* x, const int64_t* rows, int M, int K
   g.A[0] = x; g.B[0] = w; g.lda[0] = ldx; g.ldb[0] = K; g.Kc[0] = K; g.npairs = 1;
   g.a_rows = rows; g.M = M; g.N = N; g.bias0 = b; g.out0 = y; g.out1 = pre; g.ldo = N;
   g.act = act; g.lo = act_lo; g.hi = act_hi;
-  if (pl.nz <= 1 && gemm_x6_use(g) && gemm_x6_pick_bn(M, N) == 64) return launch_gemm_x6<EPI_LINEAR, 0, 64>(g, 1, stream, "linear_fwd(x6)");
-  if (pl.nz <= 1 && gemm_x6_use(g)) return launch_gemm_x6<EPI_LINEAR>(g, 1, stream, "linear_fwd(x6)");
-  if (pl.nz <= 1) return launch_gemm<true, true, EPI_LINEAR>(g, pl, stream, "linear_fwd");
-  if (ws == nullptr || ws_bytes < evae_dense_fwd_workspace_bytes(M, K, N, 0)) {
-    set_error("linear_fwd: workspace too small (%zu)", ws_bytes);
-    return EVAE_EWORKSPACE;
-  }
-  g.out0 = (float*)ws; g.out1 = nullptr;
-  int rc;
-  if (gemm_x6_use(g)) {
-    g.ksplit = pl.ksplit;
-    rc = launch_gemm_x6<EPI_RAW>(g, pl.nz, stream, "linear_fwd(split-K, x6)");
-  } else {
-    rc = launch_gemm<true, true, EPI_RAW>(g, pl, stream, "linear_fwd(split-K)");
-  }
-  if (rc) return rc;
-  FinishArgs f = {};
-  f.ones_col = -1;
-  f.part = (const float*)ws; f.nz = pl.nz; f.M = M; f.N = N; f.ldo = N; f.epi = EPI_LINEAR;
-  f.bias0 = b; f.out0 = y; f.out1 = pre; f.act = act; f.lo = act_lo; f.hi = act_hi;
-  return launch_finish(f, stream);
+  static const GemmNames nm = {"linear_fwd", "linear_fwd", "linear_fwd(x6)", "linear_fwd(split-K)", "linear_fwd(split-K, x6)"};
+  return launch_gemm_or_split<true, EPI_LINEAR>(g, pl, gemm_x6_use(g), ws, ws_bytes, stream, nm);
 }
 
 // ---- the two heads of the encoder + the sample, for thin launches -------------------------------------------------------
@@ -433,40 +397,17 @@ static int dense_bwd_data_core(const float* dy1, const float* w1, const float* d
     g.B[0] = wT; g.ldb[0] = ldt;
     if (dy2) { g.B[1] = wT + (size_t)K * ldt; g.ldb[1] = ldt; }
   }
-  if (pl.nz <= 1) {
-    const bool narrow = x6 && gemm_x6_pick_bn(M, K) == 64;
-    if (sink) {
-      if (x6 && narrow) return launch_gemm_x6<EPI_GATE_BWD_IMG, 0, 64>(g, 1, stream, "dense_bwd_data(gate, bf16 tile images, x6)");
-      if (x6) return launch_gemm_x6<EPI_GATE_BWD_IMG>(g, 1, stream, "dense_bwd_data(gate, bf16 tile images, x6)");
-      return launch_gemm<true, false, EPI_GATE_BWD_IMG>(g, pl, stream, "dense_bwd_data(gate, bf16 tile images)");
-    }
-    if (x6 && gate && narrow) return launch_gemm_x6<EPI_GATE_BWD, 0, 64>(g, 1, stream, "dense_bwd_data(gate, x6)");
-    if (x6 && gate) return launch_gemm_x6<EPI_GATE_BWD>(g, 1, stream, "dense_bwd_data(gate, x6)");
-    if (x6 && narrow) return launch_gemm_x6<EPI_LINEAR, 0, 64>(g, 1, stream, "dense_bwd_data(x6)");
-    if (x6) return launch_gemm_x6<EPI_LINEAR>(g, 1, stream, "dense_bwd_data(x6)");
-    if (gate) return launch_gemm<true, false, EPI_GATE_BWD>(g, pl, stream, "dense_bwd_data(gate)");
-    return launch_gemm<true, false, EPI_LINEAR>(g, pl, stream, "dense_bwd_data");
+  if (sink) {                                      // one launch by construction (nz = 1 above)
+    if (x6 && gemm_x6_pick_bn(M, K) == 64) return launch_gemm_x6<EPI_GATE_BWD_IMG, 0, 64>(g, 1, stream, "dense_bwd_data(gate, bf16 tile images, x6)");
+    if (x6) return launch_gemm_x6<EPI_GATE_BWD_IMG>(g, 1, stream, "dense_bwd_data(gate, bf16 tile images, x6)");
+    return launch_gemm<true, false, EPI_GATE_BWD_IMG>(g, pl, stream, "dense_bwd_data(gate, bf16 tile images)");
   }
-  if (ws == nullptr || ws_bytes < part_bytes + 256) {
-    set_error("dense_bwd_data: workspace too small (%zu)", ws_bytes);
-    return EVAE_EWORKSPACE;
-  }
-  g.out0 = (float*)ws; g.out1 = nullptr;
-  int rc;
-  if (x6) {
-    g.ksplit = pl.ksplit;
-    rc = launch_gemm_x6<EPI_RAW>(g, pl.nz, stream, "dense_bwd_data(split-K, x6)");
-  } else {
-    rc = launch_gemm<true, false, EPI_RAW>(g, pl, stream, "dense_bwd_data(split-K)");
-  }
-  if (rc) return rc;
-  FinishArgs f = {};
-  f.ones_col = -1;
-  f.part = (const float*)ws; f.nz = pl.nz; f.M = M; f.N = K; f.ldo = ldo;
-  f.epi = gate ? EPI_GATE_BWD : EPI_LINEAR; f.out0 = dx_or_dh; f.out1 = gate ? dg : nullptr;
-  f.e0 = out_prev; f.e1 = s_prev;
-  if (tsink) f.tsink = *tsink;
-  return launch_finish(f, stream);
+  static const GemmNames nm_gate = {"dense_bwd_data", "dense_bwd_data(gate)", "dense_bwd_data(gate, x6)", "dense_bwd_data(split-K)",
+                                    "dense_bwd_data(split-K, x6)"};
+  static const GemmNames nm = {"dense_bwd_data", "dense_bwd_data", "dense_bwd_data(x6)", "dense_bwd_data(split-K)",
+                               "dense_bwd_data(split-K, x6)"};
+  if (gate) return launch_gemm_or_split<false, EPI_GATE_BWD>(g, pl, x6, ws, ws_bytes, stream, nm_gate);
+  return launch_gemm_or_split<false, EPI_LINEAR>(g, pl, x6, ws, ws_bytes, stream, nm);
 }
 
 extern "C" int evae_dense_bwd_data(const float* dy1, const float* w1, const float* dy2, const float* w2,

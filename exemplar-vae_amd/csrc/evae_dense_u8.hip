@@ -25,7 +25,6 @@
 
 namespace evae {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16u __attribute__((ext_vector_type(16)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));    // native vector (HIP's uint4 struct does not always stay in registers)
 
@@ -70,27 +69,17 @@ __global__ __launch_bounds__(U8_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
   extern __shared__ __attribute__((aligned(16))) char smem[];
   int tm, tn, zs = 0;
   if constexpr (GATED) {
-    // XCD-aware bijective remap (as the fp32 GEMM): XCD x = id % 8 works on a contiguous run of tiles
-    const int ntiles = tiles_m * tiles_n;
-    const int id = blockIdx.x, xcd = id & 7, slot = id >> 3;
-    const int qq = ntiles >> 3, rr = ntiles & 7;
-    const int tile = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + slot;
+    const int tile = tile_of_block(blockIdx.x, tiles_m * tiles_n);
     tm = tile / tiles_n; tn = tile - tm * tiles_n;
   } else {
-    // Split-K weight gradient: the tiles_m row tiles (pixels) of one UNIT = (contraction slice z, column tile tn) read the same
-    // three-term dy^T images -- the heavy operand, 6 bytes per element -- so a unit's blocks sit on ONE XCD, dispatched
-    // back to back (ids 8 j + x -> XCD x): they walk the slice in step and all but the first find every image slab in that
-    // XCD's L2.  Units are ordered z-major and dealt to the XCDs in contiguous runs, so the column tiles of a slice (which
-    // share the byte rows) mostly meet on one XCD too.  (r02: every (row tile x column tile x slice) block streamed both
-    // operands past its XCD's L2: 710 MB read per launch against 110 MB of operands.)
-    const int nunits = ((nslab_total + ksplit - 1) / ksplit) * tiles_n;      // slices x column tiles; the grid is 1-D
-    const int id = blockIdx.x, xcd = id & 7, slot = id >> 3;
-    const int qq = nunits >> 3, rr = nunits & 7;
-    const int ul = slot / tiles_m;
-    if (ul >= qq + (xcd < rr ? 1 : 0)) return;                // this XCD has one unit less than the grid allows for
-    const int u = xcd * qq + (xcd < rr ? xcd : rr) + ul;
-    tm = slot - ul * tiles_m;
-    zs = u / tiles_n; tn = u - zs * tiles_n;
+    // Split-K weight gradient: a unit = the tiles_m row tiles (pixels) of one (slice, column tile), which share the three-term
+    // dy^T images -- the heavy operand, 6 bytes per element
+    const int nunits = ((nslab_total + ksplit - 1) / ksplit) * tiles_n;      // slices x column tiles
+    const BlockPlace b = block_place(blockIdx.x);
+    if (unit_block_idle(b, nunits, tiles_m)) return;
+    const UnitSlot us = unit_of_block(b, nunits, tiles_m);
+    tm = us.idx;
+    zs = us.unit / tiles_n; tn = us.unit - zs * tiles_n;
   }
   const int m0 = tm * U8_BM, n0 = tn * (GATED ? U8_BN : 2 * U8_BN);
   const int s_begin = zs * ksplit;
@@ -280,10 +269,7 @@ __global__ __launch_bounds__(NWR * 128) __attribute__((amdgpu_waves_per_eu(2, 2)
   char* const Bbuf = smem + 4 * U8P_A;           // [L][3 terms][128 columns][64 B swizzled] = the weight image of a slab
   int tm, tn;
   {
-    const int ntiles = tiles_m * tiles_n;
-    const int id = blockIdx.x, xcd = id & 7, slot = id >> 3;
-    const int qq = ntiles >> 3, rr = ntiles & 7;
-    const int tile = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + slot;
+    const int tile = tile_of_block(blockIdx.x, tiles_m * tiles_n);
     tm = tile / tiles_n; tn = tile - tm * tiles_n;
   }
   const int m0 = tm * BM, n0 = tn * U8_BN;
@@ -566,15 +552,15 @@ static int gated_dense_fwd_u8_core(const unsigned char* x, const int64_t* rows, 
     // a machine-filling launch: the copy-pipeline form of the same kernel; 256-row blocks when those still fill the machine
     const int tiles_m4 = cdiv(M, 256);
     if (tall && (tall == 2 || tiles_m4 * tiles_n >= 256)) {
-      u8p_gemm_kernel<4, 2><<<tiles_m4 * tiles_n, 512, u8p_lds_bytes(4, 2), (hipStream_t)stream_>>>(
+      u8p_gemm_kernel<4, 2><<<tile_grid(tiles_m4 * tiles_n), 512, u8p_lds_bytes(4, 2), (hipStream_t)stream_>>>(
           x, rows, M, ldx, x_scale, (const unsigned short*)prepared, u8_nslab(K), bh, bg, N, out, save_s, tiles_m4, tiles_n, tsink);
       return check_launch("u8p_gemm_kernel<4, 2>");
     }
-    u8p_gemm_kernel<2, 2><<<tiles_m * tiles_n, 256, u8p_lds_bytes(2, 2), (hipStream_t)stream_>>>(
+    u8p_gemm_kernel<2, 2><<<tile_grid(tiles_m * tiles_n), 256, u8p_lds_bytes(2, 2), (hipStream_t)stream_>>>(
         x, rows, M, ldx, x_scale, (const unsigned short*)prepared, u8_nslab(K), bh, bg, N, out, save_s, tiles_m, tiles_n, tsink);
     return check_launch("u8p_gemm_kernel<2, 2>");
   }
-  u8_gemm_kernel<true><<<tiles_m * tiles_n, U8_NT, 2 * U8_STAGE, (hipStream_t)stream_>>>(
+  u8_gemm_kernel<true><<<tile_grid(tiles_m * tiles_n), U8_NT, 2 * U8_STAGE, (hipStream_t)stream_>>>(
       x, rows, M, ldx, x_scale, (const unsigned short*)prepared, u8_nslab(K), u8_nslab(K), bh, bg, N, out, save_s, tiles_m, tiles_n,
       tsink);
   return check_launch("u8_gemm_kernel<gated>");
@@ -675,8 +661,7 @@ static int dense_bwd_weight_u8_core(const float* dy, int M, int N, long long ldy
     (void)hipFuncSetAttribute((const void*)u8_gemm_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * U8_STAGE);
     attr = true;
   }
-  const int units = L.nz * L.tiles_n;
-  u8_gemm_kernel<false><<<8 * L.tiles_k * cdiv(units, 8), U8_NT, 2 * U8_STAGE, stream>>>(
+  u8_gemm_kernel<false><<<unit_grid(L.nz * L.tiles_n, L.tiles_k), U8_NT, 2 * U8_STAGE, stream>>>(
       xT, nullptr, K + 1, L.ldt, 1.0f, img, L.nslab, L.ksplit, nullptr, nullptr, N, part, nullptr, L.tiles_k, L.tiles_n,
       P6Sink{nullptr, 0, 0, 0, 0});
   rc = check_launch("u8_gemm_kernel<raw>");

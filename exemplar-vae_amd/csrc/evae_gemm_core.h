@@ -5,6 +5,7 @@
 
 #include "evae_common.h"
 #include "evae_p6_image.h"
+#include "evae_tile_map.h"
 
 namespace evae {
 

@@ -681,26 +681,16 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g, const int blk_x, co
 
   int tm, tn, zslice = blk_z;
   if (g.sk_local) {
-    // XCD-local split-K (1-D grid): a UNIT = the tiles_n column tiles of one (contraction slice, row tile) -- they read the
-    // same A tile -- sits on one XCD, dispatched back to back (ids 8 j + x -> XCD x), so its blocks walk the slice in step
-    // and share every A slab through that XCD's L2; units are ordered slice-major and dealt to the XCDs in contiguous runs,
-    // so the row tiles of a slice (sharing B) mostly meet on one XCD as well.  (r02: a split-K launch's grid (tiles, 1, nz)
-    // scattered the blocks of a slice over all eight L2s: 346 MB read against 91 MB of operands for the layer-2 weight
-    // gradient.)
-    const int nunits = g.sk_local * g.tiles_m;                // sk_local = number of slices
-    const int id = blk_x, xcd = id & 7, slot = id >> 3;
-    const int qq = nunits >> 3, rr = nunits & 7;
-    const int ul = slot / g.tiles_n;
-    if (ul >= qq + (xcd < rr ? 1 : 0)) return;
-    const int u = xcd * qq + (xcd < rr ? xcd : rr) + ul;
-    tn = slot - ul * g.tiles_n;
-    zslice = u / g.tiles_m; tm = u - zslice * g.tiles_m;
+    // XCD-local split-K: a unit = the tiles_n column tiles of one (slice, row tile), which share the A tile; sk_local = slices
+    const int nunits = g.sk_local * g.tiles_m;
+    const BlockPlace b = block_place(blk_x);
+    if (unit_block_idle(b, nunits, g.tiles_n)) return;
+    const UnitSlot us = unit_of_block(b, nunits, g.tiles_n);
+    tn = us.idx;
+    zslice = us.unit / g.tiles_m; tm = us.unit - zslice * g.tiles_m;
   } else {
-    // XCD-aware bijective remap: XCD x (= id % 8) works on a contiguous run of tiles
     const int ntiles = g.tiles_m * g.tiles_n;
-    const int id = blk_x, xcd = id & 7, slot = id >> 3;
-    const int qq = ntiles >> 3, rr = ntiles & 7;
-    const int tile = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + slot;
+    const int tile = tile_of_block(block_place(blk_x), ntiles);
     tm = tile / g.tiles_n; tn = tile - tm * g.tiles_n;
   }
   const int m0 = tm * BM;
@@ -1203,10 +1193,10 @@ static int launch_gemm_w(GemmArgs& g, int nz, hipStream_t stream, const char* wh
   constexpr bool GATED = (EPI == EPI_GATED || EPI == EPI_RAW_GATED);
   g.tiles_m = cdiv(g.M, BM);
   g.tiles_n = cdiv(g.N, GATED ? 64 : BN_);
-  dim3 grid(g.tiles_m * g.tiles_n, 1, nz);
+  dim3 grid(tile_grid(g.tiles_m * g.tiles_n), 1, nz);
   if (g.sk_local > 0) {
     if (g.sk_local != nz || g.ksplit <= 0) { set_error("%s: XCD-local split-K needs sk_local == nz and a split contraction", what); return EVAE_EINVAL; }
-    grid = dim3(8 * g.tiles_n * cdiv(nz * g.tiles_m, 8), 1, 1);
+    grid = dim3(unit_grid(nz * g.tiles_m, g.tiles_n), 1, 1);
   }
   {
     static int dbg = -1;

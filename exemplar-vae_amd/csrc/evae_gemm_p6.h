@@ -43,7 +43,6 @@
 
 namespace evae {
 
-typedef __bf16 p6_bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 p6_bf16x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void* p6_lds_t;
 typedef __attribute__((address_space(3))) p6_bf16x4* p6_lds4_t;
@@ -57,10 +56,9 @@ constexpr int p6_lds_bytes(int bn) { return P6_NS * p6_stage_bytes(bn); }     //
 // twelve times per k-step (measured: the forward GEMM 98 us instead of 58).  The kernel's own waits cover it: every fragment
 // is read one iteration before its use, behind the barrier that follows the wait for its k-step's copies, and is consumed
 // behind the next iteration's s_waitcnt lgkmcnt(0).
-typedef unsigned p6_u32x2 __attribute__((ext_vector_type(2)));
 template <int OFF>
-__device__ __forceinline__ p6_u32x2 p6_tr_read(unsigned lds_addr) {
-  p6_u32x2 r;
+__device__ __forceinline__ u32x2 p6_tr_read(unsigned lds_addr) {
+  u32x2 r;
   asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(r) : "v"(lds_addr), "n"(OFF));
   return r;
 }
@@ -81,20 +79,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   char* const lds = reinterpret_cast<char*>(smem);
   const int ntiles = g.tiles_m * g.tiles_n;
   int tile, zs = blockIdx.z;
-  if (g.sk_local > 0) {
-    // split contraction, XCD-local (r04): 1-D grid of 8 * ceil(slices / 8) * ntiles blocks; XCD x (= block id mod 8) runs ALL the
-    // tiles of slices x, x + 8, ...: the blocks that share a slice's operand strips sit on one L2 and walk the slice in step
-    // (PMC of the 3-D grid at 600 x 301 x 25 100: 478 MB per launch against 135 MB of operand images, 7.4 TB/s -- every XCD met
-    // every slice)
-    const int id = blockIdx.x, xcd = id & 7, slot = id >> 3;
-    const int j = slot / ntiles;
-    tile = slot - j * ntiles;
-    zs = xcd + 8 * j;
-    if (zs >= g.sk_local) return;
+  if (g.sk_local > 0) {       // split contraction, XCD-local: sk_local = slices
+    const BlockPlace b = block_place(blockIdx.x);
+    const SliceTile st = slice_of_block(b, ntiles);
+    tile = st.tile; zs = st.slice;
+    if (slice_block_idle(b, ntiles, g.sk_local)) return;
   } else {
-    const int id = blockIdx.x, xcd = id & 7, slot = id >> 3;
-    const int qq = ntiles >> 3, rr = ntiles & 7;
-    tile = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + slot;
+    tile = tile_of_block(block_place(blockIdx.x), ntiles);
   }
   const int tm = tile / g.tiles_n, tn = tile - tm * g.tiles_n;
   const int m0 = tm * BM;
@@ -207,26 +198,26 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   }
 
   const unsigned lds_base = (unsigned)(uintptr_t)(p6_lds_t)lds;          // LDS byte address of the ring
-  p6_bf16x8 af[2][MT][3], bf[2][NT][3];
+  bf16x8 af[2][MT][3], bf[2][NT][3];
   auto read_a = [&](auto par_, int b, int mt, int p) {
     constexpr int par = decltype(par_)::value;
     if constexpr (TA) {
       // k rows c and c + 4 differ by 128 bytes (the rotation c ^ 4 ib flips bit 2 of both alike: XOR it into the offset)
       const unsigned a0 = lds_base + (unsigned)(b * SB) + fa[mt], a1 = lds_base + (unsigned)(b * SB) + (fa[mt] ^ 128u);
-      p6_u32x2 lo, hi;
+      u32x2 lo, hi;
       if (p == 0) { lo = p6_tr_read<0>(a0); hi = p6_tr_read<0>(a1); }
       else if (p == 1) { lo = p6_tr_read<P6_PLANE>(a0); hi = p6_tr_read<P6_PLANE>(a1); }
       else { lo = p6_tr_read<2 * P6_PLANE>(a0); hi = p6_tr_read<2 * P6_PLANE>(a1); }
       typedef unsigned u32x4_ __attribute__((ext_vector_type(4)));
       const u32x4_ v = {lo[0], lo[1], hi[0], hi[1]};
-      af[par][mt][p] = __builtin_bit_cast(p6_bf16x8, v);
+      af[par][mt][p] = __builtin_bit_cast(bf16x8, v);
     } else {
-      af[par][mt][p] = *reinterpret_cast<const p6_bf16x8*>(lds + b * SB + fa[mt] + p * P6_PLANE);
+      af[par][mt][p] = *reinterpret_cast<const bf16x8*>(lds + b * SB + fa[mt] + p * P6_PLANE);
     }
   };
   auto read_b = [&](auto par_, int b, int nt, int p) {
     constexpr int par = decltype(par_)::value;
-    bf[par][nt][p] = *reinterpret_cast<const p6_bf16x8*>(lds + b * SB + fb[nt] + p * BPL);
+    bf[par][nt][p] = *reinterpret_cast<const bf16x8*>(lds + b * SB + fb[nt] + p * BPL);
   };
   auto read_all = [&](auto par_, int b) {
 #pragma unroll
@@ -346,10 +337,10 @@ static int launch_gemm_p6(GemmArgs& g, int nz, hipStream_t stream, const char* w
   constexpr bool GATED = (EPI == EPI_GATED || EPI == EPI_RAW_GATED);
   g.tiles_m = cdiv(g.M, BM);
   g.tiles_n = cdiv(g.N, GATED ? 64 : BN_);
-  dim3 grid(g.tiles_m * g.tiles_n, 1, nz);
+  dim3 grid(tile_grid(g.tiles_m * g.tiles_n), 1, nz);
   if (g.sk_local > 0) {
     if (g.sk_local != nz || g.ksplit <= 0) { set_error("%s: XCD-local split needs sk_local == nz and a split contraction", what); return EVAE_EINVAL; }
-    grid = dim3(8 * cdiv(nz, 8) * g.tiles_m * g.tiles_n, 1, 1);
+    grid = dim3(slice_grid(g.tiles_m * g.tiles_n, nz), 1, 1);
   }
   gemm_p6_kernel<EPI, BN_, TA><<<grid, 256, p6_lds_bytes(BN_), stream>>>(g);
   return check_launch(what);

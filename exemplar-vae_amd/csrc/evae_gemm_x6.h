@@ -26,11 +26,6 @@
 
 namespace evae {
 
-typedef __bf16 x6_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 x6_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float x6_f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned x6_u32x2 __attribute__((ext_vector_type(2)));
-
 #ifndef EVAE_X6_ABL
 #define EVAE_X6_ABL 0
 #endif
@@ -38,18 +33,7 @@ constexpr int X6_ABL = EVAE_X6_ABL;         // ablation builds (tools only): 1 =
 constexpr int X6_PLANE = 128 * 64;          // bytes of one plane: 128 rows x 32 bf16
 constexpr int x6_lds_bytes(int bn) { return 3 * X6_PLANE + 3 * bn * 64; }     // 48 KB (column tile 128) or 36 KB (64)
 
-// two consecutive fp32 -> the three bf16 terms of each, packed pairwise (9 VALU instructions: 3 v_cvt_pk_bf16_f32, 2 x (shift,
-// mask, v_pk_add_f32))
-__device__ __forceinline__ void x6_split2(float x, float y, unsigned& p0, unsigned& p1, unsigned& p2) {
-  x6_f32x2 r = {x, y};
-  p0 = __builtin_bit_cast(unsigned, __builtin_convertvector(r, x6_bf16x2));
-  x6_f32x2 h = {__uint_as_float(p0 << 16), __uint_as_float(p0 & 0xFFFF0000u)};
-  r = r - h;                                                   // exact: a0 carries the leading bits of a
-  p1 = __builtin_bit_cast(unsigned, __builtin_convertvector(r, x6_bf16x2));
-  h[0] = __uint_as_float(p1 << 16); h[1] = __uint_as_float(p1 & 0xFFFF0000u);
-  r = r - h;
-  p2 = __builtin_bit_cast(unsigned, __builtin_convertvector(r, x6_bf16x2));
-}
+// (the split of two consecutive fp32 into the three packed bf16 terms: p6_split2, evae_p6_image.h)
 
 // TM = terms per operand.  3: the fp32-accurate product above.  2 (the top-K screen only, whose distances are a filter with a
 // proven error bound, re-ranked exactly afterwards): a = a0 + a1, products a0 b0 + a0 b1 + a1 b0 -- half the MFMAs, two thirds
@@ -70,13 +54,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   if constexpr (EPI == EPI_PRIOR_LSE || EPI == EPI_PRIOR_P) {
     if (g.skip_flag != nullptr && *g.skip_flag != 0u) return;
   }
-  const int ntiles = g.tiles_m * g.tiles_n;
-  int tile;
-  {
-    const int id = blockIdx.x, xcd = id & 7, slot = id >> 3;
-    const int qq = ntiles >> 3, rr = ntiles & 7;
-    tile = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + slot;
-  }
+  const int tile = tile_of_block(blockIdx.x, g.tiles_m * g.tiles_n);
   const int tm = tile / g.tiles_n, tn = tile - tm * g.tiles_n;
   const int m0 = tm * BM;
   const int n0 = GATED ? tn * 64 : tn * BN_;
@@ -178,18 +156,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int i = isb ? q - NV : q;
     const float4 v = isb ? rb[i] : ra[i];
     if (part == 0) {
-      x6_split2(v.x, v.y, sp[0], sp[1], sp[2]);
+      p6_split2(v.x, v.y, sp[0], sp[1], sp[2]);
       if constexpr (NORMS) { if (!isb) nrm[i] = fmaf(v.y, v.y, fmaf(v.x, v.x, nrm[i])); }
     } else if (part == 1) {
-      x6_split2(v.z, v.w, sp[3], sp[4], sp[5]);
+      p6_split2(v.z, v.w, sp[3], sp[4], sp[5]);
       if constexpr (NORMS) { if (!isb) nrm[i] = fmaf(v.w, v.w, fmaf(v.z, v.z, nrm[i])); }
     } else {
       char* p = lds + (isb ? 3 * X6_PLANE : 0) + st_off[i];
       const int ps = isb ? BN_ * 64 : X6_PLANE;                    // bytes between the planes of this operand
-      x6_u32x2 t0 = {sp[0], sp[3]}, t1 = {sp[1], sp[4]}, t2 = {sp[2], sp[5]};
-      *reinterpret_cast<x6_u32x2*>(p) = t0;
-      *reinterpret_cast<x6_u32x2*>(p + ps) = t1;
-      if constexpr (TM == 3) *reinterpret_cast<x6_u32x2*>(p + 2 * ps) = t2;
+      u32x2 t0 = {sp[0], sp[3]}, t1 = {sp[1], sp[4]}, t2 = {sp[2], sp[5]};
+      *reinterpret_cast<u32x2*>(p) = t0;
+      *reinterpret_cast<u32x2*>(p + ps) = t1;
+      if constexpr (TM == 3) *reinterpret_cast<u32x2*>(p + 2 * ps) = t2;
     }
   };
   auto stage = [&](int q) { stage_part(q, 0); stage_part(q, 1); stage_part(q, 2); };
@@ -220,17 +198,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #define EVAE_SB __builtin_amdgcn_sched_barrier(0)
     auto slab = [&](int s, auto ST_, auto LD_) {
       constexpr bool ST = decltype(ST_)::value, LD = decltype(LD_)::value;
-      x6_bf16x8 af[2][MT][TM], bf[2][NT][TM];
+      bf16x8 af[2][MT][TM], bf[2][NT][TM];
 #pragma unroll
       for (int step = 0; step < 2; ++step) {
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-          for (int p = 0; p < TM; ++p) af[step][mt][p] = *reinterpret_cast<const x6_bf16x8*>(lds + fa[step][mt] + p * X6_PLANE);
+          for (int p = 0; p < TM; ++p) af[step][mt][p] = *reinterpret_cast<const bf16x8*>(lds + fa[step][mt] + p * X6_PLANE);
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
-          for (int p = 0; p < TM; ++p) bf[step][nt][p] = *reinterpret_cast<const x6_bf16x8*>(lds + fb[step][nt] + p * (BN_ * 64));
+          for (int p = 0; p < TM; ++p) bf[step][nt][p] = *reinterpret_cast<const bf16x8*>(lds + fb[step][nt] + p * (BN_ * 64));
       }
       if constexpr (ST) __syncthreads();             // every wave holds its fragments: the planes may be overwritten
       __builtin_amdgcn_s_setprio(1);                 // the MFMA phase ahead of the other block's fragment reads
@@ -316,13 +294,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   constexpr unsigned OOB = 0x80000000u;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   char* const lds = reinterpret_cast<char*>(smem);
-  const int ntiles = g.tiles_m * g.tiles_n;
-  int tile;
-  {
-    const int id = blockIdx.x, xcd = id & 7, slot = id >> 3;
-    const int qq = ntiles >> 3, rr = ntiles & 7;
-    tile = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + slot;
-  }
+  const int tile = tile_of_block(blockIdx.x, g.tiles_m * g.tiles_n);
   const int tm = tile / g.tiles_n, tn = tile - tm * g.tiles_n;
   const int m0 = tm * BM, n0 = tn * BN_;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -391,7 +363,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     unsigned p0, p1, p2;
     const float x = isa ? comp(ra[2 * pair], i) : comp(rb[2 * pair], i);
     const float y = isa ? comp(ra[2 * pair + 1], i) : comp(rb[2 * pair + 1], i);
-    x6_split2(x, y, p0, p1, p2);
+    p6_split2(x, y, p0, p1, p2);
     char* p = lds + (isa ? 0 : 3 * X6_PLANE) + st_off[i] + 4 * pair;
     *reinterpret_cast<unsigned*>(p) = p0;
     *reinterpret_cast<unsigned*>(p + X6_PLANE) = p1;
@@ -449,17 +421,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     __syncthreads();
     auto slab = [&](int s, auto ST_, auto LD_) {
       constexpr bool ST = decltype(ST_)::value, LD = decltype(LD_)::value;
-      x6_bf16x8 af[2][MT][3], bf[2][NT][3];
+      bf16x8 af[2][MT][3], bf[2][NT][3];
 #pragma unroll
       for (int step = 0; step < 2; ++step) {
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-          for (int p = 0; p < 3; ++p) af[step][mt][p] = *reinterpret_cast<const x6_bf16x8*>(lds + fa[step][mt] + p * X6_PLANE);
+          for (int p = 0; p < 3; ++p) af[step][mt][p] = *reinterpret_cast<const bf16x8*>(lds + fa[step][mt] + p * X6_PLANE);
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
-          for (int p = 0; p < 3; ++p) bf[step][nt][p] = *reinterpret_cast<const x6_bf16x8*>(lds + fb[step][nt] + p * X6_PLANE);
+          for (int p = 0; p < 3; ++p) bf[step][nt][p] = *reinterpret_cast<const bf16x8*>(lds + fb[step][nt] + p * X6_PLANE);
       }
       if constexpr (ST) __syncthreads();
       __builtin_amdgcn_s_setprio(1);
@@ -533,7 +505,7 @@ static int launch_gemm_x6t(GemmArgs& g, int nz, hipStream_t stream, const char* 
   g.tiles_m = cdiv(g.M, BM);
   g.tiles_n = cdiv(g.N, 128);
   g.dbg = 0;
-  dim3 grid(g.tiles_m * g.tiles_n, 1, nz);
+  dim3 grid(tile_grid(g.tiles_m * g.tiles_n), 1, nz);
   gemm_x6t_kernel<EPI, CV><<<grid, 256, x6_lds_bytes(128), stream>>>(g);
   return check_launch(what);
 }
@@ -594,9 +566,46 @@ static int launch_gemm_x6(GemmArgs& g, int nz, hipStream_t stream, const char* w
   g.tiles_m = cdiv(g.M, BM);
   g.tiles_n = cdiv(g.N, GATED ? 64 : BN_);
   g.dbg = 0;
-  dim3 grid(g.tiles_m * g.tiles_n, 1, nz);
+  dim3 grid(tile_grid(g.tiles_m * g.tiles_n), 1, nz);
   gemm_x6_kernel<EPI, CV, BN_, TM><<<grid, 256, x6_lds_bytes(BN_), stream>>>(g);
   return check_launch(what);
+}
+
+// ---- a planned GEMM with epilogue EPI (EPI_GATED, EPI_LINEAR, EPI_GATE_BWD), A contraction-contiguous, on either pipe (x6: the
+// caller's choice): ONE launch when the plan does not split the contraction; otherwise raw partial planes [nz][1 or 2][M][N]
+// into the workspace (EPI_RAW / EPI_RAW_GATED), then launch_finish with the epilogue's operands taken from the same GemmArgs.
+// (here and not beside launch_finish: this is the first header that sees both pipes' launchers)
+struct GemmNames { const char* entry; const char* direct; const char* direct_x6; const char* split; const char* split_x6; };
+
+template <bool B_KC, int EPI>
+static int launch_gemm_or_split(GemmArgs& g, const Plan& pl, bool x6, void* ws, size_t ws_bytes, hipStream_t stream, const GemmNames& nm) {
+  constexpr bool GATED = (EPI == EPI_GATED);
+  if (pl.nz <= 1) {
+    if constexpr (!GATED) {
+      if (x6 && gemm_x6_pick_bn(g.M, g.N) == 64) return launch_gemm_x6<EPI, 0, 64>(g, 1, stream, nm.direct_x6);
+    }
+    if (x6) return launch_gemm_x6<EPI>(g, 1, stream, nm.direct_x6);
+    return launch_gemm<true, B_KC, EPI>(g, pl, stream, nm.direct);
+  }
+  if (ws == nullptr || ws_bytes < align_up((size_t)pl.nz * (GATED ? 2 : 1) * g.M * g.N * sizeof(float), 256) + 256) {
+    set_error("%s: workspace too small (%zu)", nm.entry, ws_bytes);
+    return EVAE_EWORKSPACE;
+  }
+  FinishArgs f = {};
+  f.ones_col = -1;
+  f.part = (const float*)ws; f.nz = pl.nz; f.M = g.M; f.N = g.N; f.ldo = g.ldo; f.epi = EPI;
+  f.bias0 = g.bias0; f.bias1 = g.bias1; f.out0 = g.out0; f.out1 = g.out1; f.out2 = g.out2; f.e0 = g.e0; f.e1 = g.e1;
+  f.act = g.act; f.lo = g.lo; f.hi = g.hi; f.tsink = g.tsink;
+  g.out0 = (float*)ws; g.out1 = g.out2 = nullptr;
+  int rc;
+  if (x6) {
+    g.ksplit = pl.ksplit;
+    rc = launch_gemm_x6<GATED ? EPI_RAW_GATED : EPI_RAW>(g, pl.nz, stream, nm.split_x6);
+  } else {
+    rc = launch_gemm<true, B_KC, GATED ? EPI_RAW_GATED : EPI_RAW>(g, pl, stream, nm.split);
+  }
+  if (rc) return rc;
+  return launch_finish(f, stream);
 }
 
 }  // namespace evae

@@ -28,31 +28,39 @@ __host__ __device__ inline size_t p6_off(int r, int k, int nks) {
   return ((size_t)(r >> 4) * nks + (k >> 4)) * P6_GROUP + (size_t)((r & 15) * 32 + ((((k >> 3) & 1) ^ ((r >> 3) & 1)) << 4) + (k & 7) * 2);
 }
 
-// round-to-nearest three-term split a = a0 + a1 + a2 (bf16 each; exact: 3 x 8 significant bits) of one fp32
-__device__ __forceinline__ unsigned p6_rn(float f) {
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+
+// The three-term split a = a0 + a1 + a2, a0 = bf16(a), a1 = bf16(a - a0), a2 = bf16(a - a0 - a1), round-to-nearest-even (exact:
+// 3 x 8 significant bits) -- the ONE definition behind the split-bf16 kernels (evae_gemm_x6.h), the pre-split images below and
+// the byte layer's weight images (evae_u8_prepare.h), which are held to the same bar and feed each other's images.
+__device__ __forceinline__ unsigned short bf16_rn(float f) {
   unsigned u = __float_as_uint(f);
   u += 0x7FFFu + ((u >> 16) & 1u);
-  return u >> 16;
+  return (unsigned short)(u >> 16);
 }
+__device__ __forceinline__ float bf16_f(unsigned short h) { return __uint_as_float((unsigned)h << 16); }
+// ... of one fp32
 __device__ __forceinline__ void p6_split1(float x, unsigned short& t0, unsigned short& t1, unsigned short& t2) {
-  const unsigned a0 = p6_rn(x);
-  const float r1 = x - __uint_as_float(a0 << 16);
-  const unsigned a1 = p6_rn(r1);
-  const float r2 = r1 - __uint_as_float(a1 << 16);
-  t0 = (unsigned short)a0; t1 = (unsigned short)a1; t2 = (unsigned short)p6_rn(r2);
+  t0 = bf16_rn(x);
+  const float r1 = x - bf16_f(t0);
+  t1 = bf16_rn(r1);
+  const float r2 = r1 - bf16_f(t1);
+  t2 = bf16_rn(r2);
 }
-// ... of two (hardware conversion, v_cvt_pk_bf16_f32): term q of x in the low half of p[q], of y in the high half
+// ... of two consecutive fp32, packed pairwise: term q of x in the low half of p[q], of y in the high half (9 VALU instructions:
+// 3 v_cvt_pk_bf16_f32, 2 x (shift, mask, v_pk_add_f32))
 __device__ __forceinline__ void p6_split2(float x, float y, unsigned& p0, unsigned& p1, unsigned& p2) {
-  typedef __bf16 bf16x2_ __attribute__((ext_vector_type(2)));
-  typedef float f32x2_ __attribute__((ext_vector_type(2)));
-  f32x2_ r = {x, y};
-  p0 = __builtin_bit_cast(unsigned, __builtin_convertvector(r, bf16x2_));
-  f32x2_ h = {__uint_as_float(p0 << 16), __uint_as_float(p0 & 0xFFFF0000u)};
-  r = r - h;
-  p1 = __builtin_bit_cast(unsigned, __builtin_convertvector(r, bf16x2_));
+  f32x2 r = {x, y};
+  p0 = __builtin_bit_cast(unsigned, __builtin_convertvector(r, bf16x2));
+  f32x2 h = {__uint_as_float(p0 << 16), __uint_as_float(p0 & 0xFFFF0000u)};
+  r = r - h;                                                   // exact: a0 carries the leading bits of a
+  p1 = __builtin_bit_cast(unsigned, __builtin_convertvector(r, bf16x2));
   h[0] = __uint_as_float(p1 << 16); h[1] = __uint_as_float(p1 & 0xFFFF0000u);
   r = r - h;
-  p2 = __builtin_bit_cast(unsigned, __builtin_convertvector(r, bf16x2_));
+  p2 = __builtin_bit_cast(unsigned, __builtin_convertvector(r, bf16x2));
 }
 
 // Where an epilogue leaves X^T's image: X's column c = image row row0 + c, X's row m = image k index kbase + m (kbase a multiple

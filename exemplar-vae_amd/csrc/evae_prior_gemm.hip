@@ -159,12 +159,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   };
   auto stage_chunk = [&](char* p, const float4 v) {
     unsigned a0, a1, a2, b0, b1, b2;
-    x6_split2(v.x, v.y, a0, a1, a2);
-    x6_split2(v.z, v.w, b0, b1, b2);
-    x6_u32x2 t0 = {a0, b0}, t1 = {a1, b1}, t2 = {a2, b2};
-    *reinterpret_cast<x6_u32x2*>(p) = t0;
-    *reinterpret_cast<x6_u32x2*>(p + X6_PLANE) = t1;
-    *reinterpret_cast<x6_u32x2*>(p + 2 * X6_PLANE) = t2;
+    p6_split2(v.x, v.y, a0, a1, a2);
+    p6_split2(v.z, v.w, b0, b1, b2);
+    u32x2 t0 = {a0, b0}, t1 = {a1, b1}, t2 = {a2, b2};
+    *reinterpret_cast<u32x2*>(p) = t0;
+    *reinterpret_cast<u32x2*>(p + X6_PLANE) = t1;
+    *reinterpret_cast<u32x2*>(p + 2 * X6_PLANE) = t2;
   };
   // fragment offsets inside a 128-row plane: rows of this lane, 16-byte slot of k-step `step` (0 / 1)
   unsigned fa[2][2], fb[2][2];
@@ -200,14 +200,14 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   };
   if (tile_begin < tile_end) load_tile(tile_begin);
   __syncthreads();
-  x6_bf16x8 bq[KS][2][3];
+  bf16x8 bq[KS][2][3];
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
       for (int p = 0; p < 3; ++p)
-        bq[ks][nt][p] = *reinterpret_cast<const x6_bf16x8*>(Ep + (wc >> 1) * NS * SLAB + (ks >> 1) * SLAB + p * X6_PLANE + fb[ks & 1][nt]);
+        bq[ks][nt][p] = *reinterpret_cast<const bf16x8*>(Ep + (wc >> 1) * NS * SLAB + (ks >> 1) * SLAB + p * X6_PLANE + fb[ks & 1][nt]);
   __syncthreads();              // every wave holds its query fragments: the planes become the exemplar buffers
 
   float tm_[2] = {-INFINITY, -INFINITY}, ssum[2] = {0.f, 0.f};       // running max of t and sum exp(t - max) per query column
@@ -234,12 +234,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
-      x6_bf16x8 af[2][3];
+      bf16x8 af[2][3];
 #pragma unroll
       for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
         for (int p = 0; p < 3; ++p)
-          af[mt][p] = *reinterpret_cast<const x6_bf16x8*>(Eb + (ks >> 1) * SLAB + p * X6_PLANE + fa[ks & 1][mt]);
+          af[mt][p] = *reinterpret_cast<const bf16x8*>(Eb + (ks >> 1) * SLAB + p * X6_PLANE + fa[ks & 1][mt]);
 #pragma unroll
       for (int tt = 0; tt < 6; ++tt)
 #pragma unroll
@@ -261,15 +261,15 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         tm_[nt] = vmax;
       }
       if (tm_[nt] != -INFINITY) {
-        const x6_f32x2 mk = {tm_[nt], tm_[nt]};
-        x6_f32x2 part = {0.f, 0.f};
+        const f32x2 mk = {tm_[nt], tm_[nt]};
+        f32x2 part = {0.f, 0.f};
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
           for (int r = 0; r < 16; r += 2) {
-            const x6_f32x2 v = {acc[mt][nt][r], acc[mt][nt][r + 1]};
-            const x6_f32x2 d = v - mk;
-            const x6_f32x2 e = {fast_exp2(d[0]), fast_exp2(d[1])};
+            const f32x2 v = {acc[mt][nt][r], acc[mt][nt][r + 1]};
+            const f32x2 d = v - mk;
+            const f32x2 e = {fast_exp2(d[0]), fast_exp2(d[1])};
             part = part + e;
           }
         ssum[nt] += part[0] + part[1];

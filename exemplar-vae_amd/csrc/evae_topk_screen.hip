@@ -350,11 +350,11 @@ template <int KS> constexpr size_t ts_lds_bytes() {
 }
 // (x, y) -> the two bf16 terms of each, term t of x in the low half of p[t]
 __device__ __forceinline__ void ts_split2(float x, float y, unsigned& p0, unsigned& p1) {
-  x6_f32x2 r = {x, y};
-  p0 = __builtin_bit_cast(unsigned, __builtin_convertvector(r, x6_bf16x2));
-  x6_f32x2 h = {__uint_as_float(p0 << 16), __uint_as_float(p0 & 0xFFFF0000u)};
+  f32x2 r = {x, y};
+  p0 = __builtin_bit_cast(unsigned, __builtin_convertvector(r, bf16x2));
+  f32x2 h = {__uint_as_float(p0 << 16), __uint_as_float(p0 & 0xFFFF0000u)};
   r = r - h;
-  p1 = __builtin_bit_cast(unsigned, __builtin_convertvector(r, x6_bf16x2));
+  p1 = __builtin_bit_cast(unsigned, __builtin_convertvector(r, bf16x2));
 }
 
 // a candidate (approximate distance, row) of query nq: the block's LDS list, or the query's global overflow list when that is full.
@@ -412,7 +412,7 @@ __global__ __launch_bounds__(TS_NT) void topk_stream_kernel(const TopkStreamArgs
   const int row_end = min(a.N, rb + a.rows_per_block);
   const int ntile = rb < row_end ? (row_end - rb + 127) / 128 : 0;
   // ---- the queries' fragments: B operand of v_mfma_f32_32x32x16_bf16, lane l: query l & 31 of the wave, k = 16 s + 8 (l >> 5) .. + 7
-  x6_bf16x8 bq[KS][2];
+  bf16x8 bq[KS][2];
   float qn = 0.f;
 #pragma unroll
   for (int s = 0; s < KS; ++s) {
@@ -425,8 +425,8 @@ __global__ __launch_bounds__(TS_NT) void topk_stream_kernel(const TopkStreamArgs
     ts_split2(v0.x, v0.y, t0[0], t1[0]); ts_split2(v0.z, v0.w, t0[1], t1[1]);
     ts_split2(v1.x, v1.y, t0[2], t1[2]); ts_split2(v1.z, v1.w, t0[3], t1[3]);
     typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    bq[s][0] = __builtin_bit_cast(x6_bf16x8, (u32x4){t0[0], t0[1], t0[2], t0[3]});
-    bq[s][1] = __builtin_bit_cast(x6_bf16x8, (u32x4){t1[0], t1[1], t1[2], t1[3]});
+    bq[s][0] = __builtin_bit_cast(bf16x8, (u32x4){t0[0], t0[1], t0[2], t0[3]});
+    bq[s][1] = __builtin_bit_cast(bf16x8, (u32x4){t1[0], t1[1], t1[2], t1[3]});
   }
   qn += __shfl_xor(qn, 32, 64);
   mark();
@@ -490,11 +490,11 @@ __global__ __launch_bounds__(TS_NT) void topk_stream_kernel(const TopkStreamArgs
       const int n_tile = (ck + 1 < NCH) ? tile : tile + 1, n_ck = (ck + 1) % NCH;
       const int f_tile = (ck + 3 < NCH) ? tile : tile + 1, f_ck = (ck + 3) % NCH;
       const bool n_live = n_tile < ntile, f_live = f_tile < ntile;
-      x6_bf16x8 a0[2], a1[2];
+      bf16x8 a0[2], a1[2];
       auto frags = [&](int buf, int s) {
         const char* src = st + (l & 31) * RS + s * 32 + 16 * half;
-        a0[buf] = *reinterpret_cast<const x6_bf16x8*>(src);
-        a1[buf] = *reinterpret_cast<const x6_bf16x8*>(src + TERM);
+        a0[buf] = *reinterpret_cast<const bf16x8*>(src);
+        a1[buf] = *reinterpret_cast<const bf16x8*>(src + TERM);
       };
       frags(0, 0);
       ts_static_for<0, KS>([&](auto S_) {

@@ -773,6 +773,28 @@ def test_empty_inputs(ops):
     torch.cuda.synchronize()
 
 
+def test_split_k_entry_points_refuse_a_workspace_that_is_too_small(ops):
+    """evae_gated_dense_fwd, evae_linear_fwd and evae_dense_bwd_data on a shape whose plan splits the contraction (300 rows, a
+    contraction of 3136: past the thin kernels' limit, 98 K-slabs over a handful of tiles): without the workspace for the partial
+    planes each returns EVAE_EWORKSPACE with its own message, before anything is launched."""
+    from evae import _lib
+    lib = _lib.load()
+    M, K, N = 300, 3136, 300
+    assert lib.evae_dense_fwd_workspace_bytes(M, K, N, 1) > 256 and lib.evae_dense_fwd_workspace_bytes(M, K, N, 0) > 256   # split plans
+    x = torch.zeros((M, K), device="cuda"); w = torch.zeros((N, K), device="cuda"); b = torch.zeros(N, device="cuda")
+    y = torch.zeros((M, N), device="cuda"); small = torch.zeros(256, dtype=torch.uint8, device="cuda")
+    P, st = ops._p, ops._stream()
+    for ws, nb in ((None, 0), (small, 256)):
+        rc = lib.evae_gated_dense_fwd(P(x), None, M, K, K, P(w), P(b), P(w), P(b), N, P(y), None, None, P(ws), nb, st)
+        assert rc == -2 and lib.evae_last_error() == b"gated_dense_fwd: workspace too small (%d)" % nb
+        rc = lib.evae_linear_fwd(P(x), None, M, K, K, P(w), P(b), N, 0, 0.0, 0.0, P(y), None, P(ws), nb, st)
+        assert rc == -2 and lib.evae_last_error() == b"linear_fwd: workspace too small (%d)" % nb
+        # dx [M x N'] = dy [M x K'] w [K' x N'] with the long contraction K' = 3136 along dy's columns
+        rc = lib.evae_dense_bwd_data(P(x), P(w.t().contiguous()), None, None, M, K, K, N, None, None, P(y), None, N, P(ws), nb, st)
+        assert rc == -2 and lib.evae_last_error() == b"dense_bwd_data: workspace too small (%d)" % nb
+    torch.cuda.synchronize()
+
+
 def test_workspace_growth_keeps_the_old_buffer_alive(ops):
     """A captured hipGraph has the workspace address baked in: a later, larger request under the same name must not free
     the buffer the graph still writes to."""

@@ -226,7 +226,9 @@ def test_p6_data_gradient_over_the_transposed_image(env, M, H):
         assert rel(res[1][0], res[0][0]) < 2e-6 and rel(res[1][1], res[0][1]) < 2e-6
 
 
-@pytest.mark.parametrize("M,N,K", [(25100, 600, 300), (2568, 600, 300), (777, 130, 90), (100, 80, 300), (4099, 24, 68)])
+# (2000, 300, 68): 129 k-steps split into 15 slices over 3 x 2 tiles -- a slice count that is no multiple of 8, so the grid of the
+# XCD-local form (evae_tile_map.h, slice_of_block) holds idle blocks
+@pytest.mark.parametrize("M,N,K", [(25100, 600, 300), (2568, 600, 300), (777, 130, 90), (100, 80, 300), (4099, 24, 68), (2000, 300, 68)])
 def test_p6_weight_gradient_over_transposed_images(env, M, N, K):
     """evae_dense_bwd_weight_p6: dW = dy^T x and db = column sums of dy from the images of dy^T and x^T (+ the all-ones row
     behind x's columns), against fp64 and against the fp32-MFMA weight gradient."""
