@@ -100,6 +100,11 @@ SIGNATURES = {
     "evae_heads_reparam_fwd": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _i, _f, _f, _p, _p, _p, _p, _p, _p, _p, _z, _p]),
     "evae_heads_reparam_fwd_bcast_applies": (_i, [_i, _i, _i, _i]),
     "evae_heads_reparam_fwd_bcast": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _i, _f, _f, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p]),
+    "evae_heads_std_applies": (_i, [_i, _i, _i, _i]),
+    "evae_heads_reparam_std_fwd": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _i, _f, _f, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "evae_heads_std_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _f, _f, _i, _i, _p, _p, _i, _p, _p, _p, _p, _i, _p, _p, _i, _p]),
+    "evae_log_normal_std_fwd": (_i, [_p, _i, _i, _p, _p]),
+    "evae_log_normal_std_bwd": (_i, [_p, _p, _i, _i, _p, _p]),
     "evae_heads_density_fwd": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _i, _f, _f, _p, _p, _p, _p, _p, _p, _z, _p]),
     "evae_log_normal_diag_bwd_hardtanh": (_i, [_p, _p, _p, _p, _f, _f, _p, _i, _i, _p, _p, _p, _p]),
     "evae_dense_bwd_data_wt_bytes": (_z, [_i, _i, _i]),

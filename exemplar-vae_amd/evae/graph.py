@@ -19,7 +19,9 @@ capture so that every replay advances its Philox offset.  RCCL collectives of th
 A VampPrior step (utils/training.py::vampprior_step_eligible) runs through the same runner with NO exemplar rows: the control
 block is [staging rows | batch indices | seed, counter | beta, step sizes], _refresh draws nothing, and the model's modular
 autograd path is what gets captured; the prologue's eps serves the `vae` model (models/BaseModel.py::_draw_eps), the prior is
-ops.MixtureLogP's launches, the ones an eager step issues.
+ops.MixtureLogP's launches, the ones an eager step issues.  A standard-normal-prior step (utils/training.py::standard_step_eligible)
+takes the same runner: `vae` captures the one-node, one-stream step of evae/fused_std.py (which reads the prologue's eps and beta from
+the hand-off), `hvae_2level` its modular path.
 
 What the model and the fused node have to know about the step that is running -- its gather list, the distinct-row tables, the
 prologue's eps, the promise that the only backward is loss.backward(ones), what the head launch already did for them -- travels
@@ -67,7 +69,7 @@ class GraphedTrainStep:
         dev = torch.device(a.device)
         D = int(torch.tensor(a.input_size).prod().item())
         # a prior without exemplar rows (the VampPrior: its components are the model's own pseudo-inputs, and number_components is
-        # NOT a number of dataset rows) has an empty head in the gather list: no draw, no distinct-row tables, nothing of the
+        # NOT a number of dataset rows; the standard-normal prior: it has no components at all) has an empty head in the gather list: no draw, no distinct-row tables, nothing of the
         # dataset is indexed with number_components
         self.no_exemplars = a.prior != 'exemplar_prior'
         C = 0 if self.no_exemplars else int(a.number_components)

@@ -2173,6 +2173,31 @@ class LogNormalDiag(torch.autograd.Function):
         return dx, dmu, dlv
 
 
+class LogNormalStandard(torch.autograd.Function):
+    """utils/distributions.py:36-41 summed over dim=1 for [B x z] inputs: LogNormalDiag with mean = logvar = 0, without the zeros."""
+
+    @staticmethod
+    def forward(ctx, x):
+        lib = _lib.load()
+        _need_cuda(x)
+        x = _f32(x)
+        B, zd = x.shape
+        out = torch.empty(B, device=x.device)
+        _lib.check(lib.evae_log_normal_std_fwd(_p(x), B, zd, _p(out), _stream()), "evae_log_normal_std_fwd")
+        ctx.save_for_backward(x)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        x, = ctx.saved_tensors
+        B, zd = x.shape
+        g = _f32(g)
+        dx = torch.empty_like(x)
+        _lib.check(lib.evae_log_normal_std_bwd(_p(x), _p(g), B, zd, _p(dx), _stream()), "evae_log_normal_std_bwd")
+        return dx
+
+
 class BernoulliLL(torch.autograd.Function):
     """utils/distributions.py:44-51 summed over dim=1: x [B x D] (no grad), mean [B x D]."""
 

@@ -16,6 +16,9 @@ MI355X kernels of libevae_hip.so (evae.ops).  What changed underneath, not in be
   (pseudo_inputs()) in place of the identity GEMM; the training step of `vae` / `hvae_2level` replays from one hipGraph
   (utils/training.py::vampprior_step_eligible), the same launches as the eager step;
   the convolutional models' step stays eager, and nothing of it is sharded.
+* the standard-normal prior (--prior standard) trains `vae` through one autograd node on one stream (evae/fused_std.py: the batch
+  rows' chain with the latent block as one launch each way, csrc/evae_latent_std.hip) and `hvae_2level` through its modular path,
+  both replayed from one hipGraph (utils/training.py::standard_step_eligible); the convolutional models' step stays eager.
 
 Out of scope: the image-generation helpers keep their names and run on plain torch ops."""
 import math
@@ -26,7 +29,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from evae import fused_vae, handoff, ops, shard
+from evae import fused_std, fused_vae, handoff, ops, shard
 from utils.distributions import (log_bernoulli, log_normal_diag, log_normal_standard, log_logistic_256,
                                  log_normal_diag_vectorized)
 from utils.nn import NonLinear, he_init, normal_init
@@ -156,10 +159,34 @@ class BaseModel(nn.Module, ABC):
                                                 bool(a.no_mask), bool(average), None if a.approximate_prior else h.rows, h.batch_staged,
                                                 approx_cache, int(a.approximate_k), *params)
 
+    def _fused_std_config(self):
+        """whether the configuration is the one evae/fused_std.py covers: MLP `vae`, standard-normal prior, binary inputs, gated
+        layers, a log-variance head (the exclusions of _fused_config)"""
+        a = self.args
+        return (getattr(self, '_use_fused', True) and a.model_name == 'vae' and a.prior == 'standard'
+                and a.input_type == 'binary' and a.no_attention is False
+                and not getattr(a, 'same_variational_var', False))
+
+    def _calculate_loss_fused_std(self, x, beta, average):
+        """The one-node, one-stream step of the standard-normal prior (evae/fused_std.py); beta and the noise come from the step's
+        hand-off when a runner installed one, as on the exemplar prior's node."""
+        h = handoff.current() or handoff.StepHandoff()
+        x2 = x.reshape(x.shape[0], -1).float()
+        eps = h.eps if h.eps is not None else getattr(self, '_eps_override', None)
+        if eps is None or tuple(eps.shape) != (x2.shape[0], self.args.z1_size):
+            eps = self._draw_eps(torch.empty((x2.shape[0], self.args.z1_size), device=x.device))
+        named = dict(self.named_parameters())
+        params = [named[n] for n in fused_std.PARAM_ORDER]
+        beta = beta if torch.is_tensor(beta) else float(beta)
+        with handoff.active(h):           # (the runner's, which is active already, or this eager step's own)
+            return fused_std.VaeStandardLoss.apply(x2, eps, beta, bool(average), *params)
+
     def calculate_loss(self, x, beta=1., average=False, exemplars_embedding=None, cache=None, dataset=None):
         x, x_indices = x
         if self._fused_path(x, x_indices, exemplars_embedding, dataset, cache):
             return self._calculate_loss_fused(x, x_indices, beta, dataset, average, cache)
+        if self._fused_std_config() and self.training and x.is_cuda and torch.is_grad_enabled():
+            return self._calculate_loss_fused_std(x, beta, average)
         x_flat = x.reshape(x.shape[0], -1) if x.dim() != 2 else x
         if self._decoder_beside_prior(x, exemplars_embedding, dataset):
             # The decoder p(x | z) and the reconstruction term need z and nothing of the prior; the prior's exemplar set (top-k over the
@@ -206,10 +233,10 @@ class BaseModel(nn.Module, ABC):
         """Standard-normal noise from the device generator (reference :81); tests override this to inject
         identical eps into the reference, the oracle and this model."""
         h = handoff.current()
-        if (h is not None and h.eps is not None and self.args.prior == 'vampprior' and self.args.model_name == 'vae'
+        if (h is not None and h.eps is not None and self.args.prior in ('vampprior', 'standard') and self.args.model_name == 'vae'
                 and self.training and tuple(h.eps.shape) == tuple(like.shape)):
-            # a captured VampPrior step of `vae`, the one model with ONE draw per step: the noise its prologue launch drew
-            # (evae/graph.py).  hvae_2level draws z2 and z1 with the same shape and must not get one buffer twice
+            # a captured VampPrior or standard-prior step of `vae`, the one model with ONE draw per step: the noise its prologue
+            # launch drew (evae/graph.py).  hvae_2level draws z2 and z1 with the same shape and must not get one buffer twice
             return h.eps
         g = getattr(self, '_eps_generator', None)      # evaluation over a sharded cache: the same stream on every rank (evae/shard.py)
         if g is not None:

@@ -48,9 +48,10 @@ def log_normal_diag(x, mean, log_var, average=False, dim=None):
 
 
 def log_normal_standard(x, average=False, dim=None):
-    """(:36-41)."""
+    """(:36-41).  The [B x z] / dim=1 / sum case is one row kernel of its own (no zero mean / log-variance tensors); other shapes
+    keep the composed formula."""
     if (not average) and dim == 1 and x.dim() == 2 and x.is_cuda:
-        return ops.LogNormalDiag.apply(x, torch.zeros_like(x), torch.zeros_like(x))
+        return ops.LogNormalStandard.apply(x)
     log_normal = -0.5 * torch.pow(x, 2) - 0.5 * log_2_pi * x.new_ones(size=x.shape)
     return torch.mean(log_normal, dim) if average else torch.sum(log_normal, dim)
 

@@ -69,11 +69,20 @@ def vampprior_step_eligible(a):
             and not bool(getattr(a, 'shard_exemplars', False)))
 
 
+def standard_step_eligible(a):
+    """Whether a standard-normal-prior training step of the configuration `a` is captured -- a function of the arguments alone,
+    the VampPrior's rule: the dense models on one device (`vae` through evae/fused_std.py's node, `hvae_2level` through its modular
+    path); the convolutional models stay eager, and so does any configuration that asks for sharding (there are no exemplars)."""
+    return (a.prior == 'standard' and a.model_name in ('vae', 'hvae_2level')
+            and not bool(getattr(a, 'shard_exemplars', False)))
+
+
 def _graphed_step(args, model, optimizer, train_loader):
     """The captured-step runner for this (model, optimizer, dataset), or None when the configuration is not
     a graph-capturable one or args.use_hip_graph is False.  Capturable: the exemplar prior (below), and the VampPrior of the
     dense models on one device (vampprior_step_eligible; convolutional models, and every process of a torch.distributed group
-    of several ranks, step eagerly) -- its step runs the modular autograd path with no exemplar rows in the runner (evae/graph.py)."""
+    of several ranks, step eagerly) -- its step runs the modular autograd path with no exemplar rows in the runner (evae/graph.py);
+    the standard-normal prior under the same condition (standard_step_eligible), `vae` through the node of evae/fused_std.py."""
     if not getattr(args, 'use_hip_graph', True) or not str(args.device).startswith('cuda'):
         return None
     a = model.args
@@ -86,6 +95,8 @@ def _graphed_step(args, model, optimizer, train_loader):
                                           (a.no_mask is False and not model._sharded() and not model._is_conv()))
     if a.prior == 'vampprior':
         ok = vampprior_step_eligible(a) and not shard.is_active()      # one device: no torch.distributed group of several ranks
+    if a.prior == 'standard':
+        ok = standard_step_eligible(a) and not shard.is_active()       # (the same condition)
     if not ok:
         return None
     # the runner keeps the optimizer and the dataset alive, so their ids cannot be recycled while it is cached

@@ -313,6 +313,30 @@ int evae_heads_reparam_fwd_bcast_applies(int M, int K, int Z, int ldx);
 int evae_heads_reparam_fwd_bcast(const float* x, int M, int K, int ldx, const float* wm, const float* bm, const float* wl,
                                  const float* bl, int Z, float lv_lo, float lv_hi, const float* eps, float* z_mean, float* lv_pre,
                                  float* logvar, float* z, float* logq, const float* src, float* dst, int n, evae_stream_t stream);
+/* The latent block of a standard-normal-prior step (--prior standard) for few rows, one launch each way (csrc/evae_latent_std.hip).
+ * evae_heads_std_applies says which (M, K, Z, ldx) the pair takes: 1 <= M <= 1024, K >= 16 a multiple of 4, ldx >= K a multiple
+ * of 4, Z <= 64; elsewhere a caller composes evae_heads_reparam_fwd + evae_log_normal_std_fwd and evae_log_normal_std_bwd +
+ * evae_reparam_logq_bwd_hardtanh + evae_dense_bwd_data.
+ * Forward: evae_heads_reparam_fwd_bcast's outputs (bit-equal where both apply; lv_pre, logq may be NULL) and
+ * logp[m] = sum_d (-z^2 / 2 - log(2 pi) / 2), the prior's density of the sample (utils/distributions.py:36-41). */
+int evae_heads_std_applies(int M, int K, int Z, int ldx);
+int evae_heads_reparam_std_fwd(const float* x, int M, int K, int ldx, const float* wm, const float* bm, const float* wl,
+                               const float* bl, int Z, float lv_lo, float lv_hi, const float* eps, float* z_mean, float* lv_pre,
+                               float* logvar, float* z, float* logq, float* logp, evae_stream_t stream);
+/* Backward of the same block: with sigma = exp(logvar / 2), dz_tot = dz + cKL z (the prior's share: -d logp / dz = z),
+ * dmu = dz_tot, dlv = dz_tot sigma eps / 2 - cKL / 2, dlv_pre = dlv where lv_lo < lv_pre < lv_hi, else 0 -- written once, row stride
+ * ldd >= Z (a merged [dmu | dlv_pre] buffer: dlv_pre = dmu + Z, ldd = 2 Z), for the heads' weight gradients -- and the data gradient
+ * dA = dmu wm + dlv_pre wl [M x K] with the gate derivative of the layer below in its epilogue, as evae_dense_bwd_data writes it:
+ * dh = dA s_prev, dg = dA out_prev (1 - s_prev), row stride ldo >= K.  cKL [M] (and neg_cKL = -cKL, may be NULL) as evae_elbo_bwd
+ * writes them; z_mean is not read (z - z_mean = sigma eps).  1 <= M <= 1024, Z <= 64, any K. */
+int evae_heads_std_bwd(const float* z_mean, const float* logvar, const float* lv_pre, const float* eps, const float* z,
+                       const float* dz, const float* cKL, const float* neg_cKL, float lv_lo, float lv_hi, int M, int Z,
+                       const float* wm, const float* wl, int K, const float* out_prev, const float* s_prev, float* dmu,
+                       float* dlv_pre, int ldd, float* dh, float* dg, int ldo, evae_stream_t stream);
+/* log N(x | 0, I) summed over dim 1 of x [B x zdim] and its backward dx = -dout x: evae_log_normal_diag_fwd / _bwd with mean =
+ * logvar = NULL, without the two zero tensors. */
+int evae_log_normal_std_fwd(const float* x, int B, int zdim, float* out, evae_stream_t stream);
+int evae_log_normal_std_bwd(const float* x, const float* dout, int B, int zdim, float* dx, evae_stream_t stream);
 /* The same two heads with the log-density of a GIVEN sample zq [M x Z] (models/AbsHModel.py:17-20 p(z1 | z2) and the
  * log_normal_diag(z1, p1_mu, p1_lv) of :99-100): logp[m] = log N(zq[m] | z_mean[m], exp(logvar[m])); workspace as above. */
 int evae_heads_density_fwd(const float* x, int M, int K, int ldx, const float* wm, const float* bm, const float* wl,

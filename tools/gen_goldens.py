@@ -950,7 +950,52 @@ def g25():
     save("g25_vampprior_epochs", **out)
 
 
+# ---- G26: two epochs of train_one_epoch under the standard-normal prior, vae and hvae_2level (G25's recipe) ----
+G26 = dict(N=80, B=16, D=64, z=8, hidden=32, warmup=4, lr=5e-4, seed=261)
+
+
+def g26():
+    """G25's recipe with --prior standard: two epochs of the reference's train_one_epoch for `vae` and `hvae_2level`, five full
+    batches per epoch of fixed binary images, no dynamic binarisation, injected eps (eps[step, 0] for vae's z / hvae's z2,
+    eps[step, 1] for hvae's z1), warmup = 4 (beta 0.25, then 0.5).  Stored: the initial state dict, the eps, per-epoch (loss, -RE, KL)
+    as train_one_epoch returns them, and the norm and sum of every final parameter."""
+    import warnings
+    from models.HVAE_2level import VAE as HVAE
+    from utils.training import train_one_epoch
+    c = G26
+    N, B, D, zm = c["N"], c["B"], c["D"], c["z"]
+    steps = 2 * (N // B)
+    x = gi.binary_images(c["seed"], N, D)
+    eps = np.random.RandomState(c["seed"] + 1).standard_normal((steps, 2, B, zm)).astype(np.float32)
+    out = {"eps": eps, "meta": np.asarray([N, B, D, zm, c["hidden"], c["warmup"]], np.int64), "lr": np.asarray(c["lr"]),
+           "seed": np.asarray(c["seed"], np.int64)}
+    ds = torch.utils.data.TensorDataset(T(x), torch.arange(N).reshape(-1, 1), torch.zeros(N))
+    loader = torch.utils.data.DataLoader(ds, batch_size=B, shuffle=False)
+    for tag, cls in (("vae", VAE), ("hvae_2level", HVAE)):
+        args = vae_args(prior="standard", model_name=tag, input_size=[1, 8, 8], hidden_size=c["hidden"], z1_size=zm, z2_size=zm,
+                        number_components=1, training_set_size=N)
+        args.batch_size, args.dynamic_binarization, args.warmup = B, False, c["warmup"]
+        torch.manual_seed(c["seed"] + 2)
+        model = cls(args)
+        for k, v in model.state_dict().items():
+            out[tag + "_sd_" + k] = v.numpy().copy()
+        per_step = 1 if tag == "vae" else 2
+        draws = iter(eps[s, k] for s in range(steps) for k in range(per_step))
+        model.reparameterize = lambda mu, logvar: T(next(draws)) * logvar.mul(0.5).exp() + mu
+        opt = AdamNormGrad(model.parameters(), lr=c["lr"])
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            out[tag + "_epoch1"] = np.asarray(train_one_epoch(1, args, loader, model, opt))
+            out[tag + "_epoch2"] = np.asarray(train_one_epoch(2, args, loader, model, opt))
+        assert next(draws, None) is None                      # every injected draw was consumed, none twice
+        for n, p_ in model.named_parameters():
+            out[tag + "_sum_" + n] = np.asarray(p_.detach().double().sum().item())
+            out[tag + "_norm_" + n] = np.asarray(p_.detach().double().norm().item())
+        print(tag, out[tag + "_epoch1"], out[tag + "_epoch2"])
+    save("g26_standard_epochs", **out)
+
+
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["g1_g2", "g3", "g4", "g5", "g6", "g6_conv", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16", "g17", "g18", "g19", "g20", "g21", "g22", "g23", "g24", "g25"]
+    which = sys.argv[1:] or ["g1_g2", "g3", "g4", "g5", "g6", "g6_conv", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16", "g17", "g18", "g19", "g20", "g21", "g22", "g23", "g24", "g25", "g26"]
     for w in which:
         globals()[w]()
