@@ -226,9 +226,16 @@ __global__ __launch_bounds__(U8_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
 // carries about 24 bytes per cycle per CU (profiles/r04_micro): at 128 rows per block the 588 MB of image reads of a
 // 25000-row launch alone take the time of the MFMAs.  NWR = 4 (eight waves, 256 rows per block, one block per CU) halves
 // the image bytes per row: 32 KB instead of 56 KB per CU and slab.
+// NWR = 7 (fourteen waves, 448 rows per block, 104 KB of LDS, still one block per CU) is for the launch whose 256-row blocks
+// need a second, part-filled round of the CUs and whose 448-row blocks need one (u8_fwd_block_rows, evae_tile_map.h: 19 968 rows
+// x 5 column tiles = 390 blocks against 225 on 256 CUs): the same wave tile and the same MFMA sequence per output element,
+// so the same bits; 38 KB copied per CU and slab.  Fourteen waves are four on two of the SIMDs: 128 registers per lane.
+// (profiles/u8fwd_tall.json: alone 64 -> 54 us, inside the replayed c2 step 84 -> 62.)
 constexpr int U8P_B = 3 * 128 * 64;
 constexpr int u8p_a_bytes(int nwr) { return nwr * 64 * 32; }
-constexpr int u8p_lds_bytes(int nwr, int lead) { return 4 * u8p_a_bytes(nwr) + lead * U8P_B; }      // lead 2: 64 KB (two blocks per CU) | 80 KB (one)
+constexpr int u8p_lds_bytes(int nwr, int lead) { return 4 * u8p_a_bytes(nwr) + lead * U8P_B; }      // lead 2: 64 KB (two blocks per CU) | 80 KB (one) | 104 KB (one)
+
+constexpr int u8p_waves(int nwr) { return nwr == 7 ? 4 : 2; }      // waves per SIMD: 2 NWR waves on four SIMDs, rounded up
 
 typedef __attribute__((address_space(3))) void* u8p_lds_t;
 typedef __attribute__((address_space(1))) const void* u8p_glb_t;
@@ -258,13 +265,18 @@ __device__ __forceinline__ void u8p_wait_vm() { asm volatile("s_waitcnt vmcnt(%0
 // the ring holds; the reads as inline assembly with hand-counted waits took the wait away, gained 2 us and failed two parity
 // tests at 10 blocks -- not kept.  profiles/r04_ab/knobs.jsonl)
 template <int NWR, int L>
-__global__ __launch_bounds__(NWR * 128) __attribute__((amdgpu_waves_per_eu(2, 2))) void u8p_gemm_kernel(
+__global__ __launch_bounds__(NWR * 128) __attribute__((amdgpu_waves_per_eu(u8p_waves(NWR), u8p_waves(NWR)))) void u8p_gemm_kernel(
     const unsigned char* __restrict__ x, const int64_t* __restrict__ rows, int M, long long ldx, float x_scale,
     const unsigned short* __restrict__ img, int nslab, const float* __restrict__ bh, const float* __restrict__ bg, int N,
     float* __restrict__ out, float* __restrict__ save_s, int tiles_m, int tiles_n, const P6Sink tsink) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int U8P_A = u8p_a_bytes(NWR), NWAVE = 2 * NWR, BM = 64 * NWR;
-  constexpr int NB = 24 / NWAVE, NB1 = NB * 2 / 3;     // B pieces per wave and slab; of them behind k-step 1
+  constexpr int NB = (24 + NWAVE - 1) / NWAVE, NB1 = NB * 2 / 3;     // B pieces per wave and slab (at most); of them behind k-step 1
+  // 14 waves: the deal is uneven, piece NB - 1 = 1 exists on waves 0 .. 9 only.  It is one of the pieces behind k-step 0, and with
+  // L = 2 every vmcnt below counts A copies and the NB1 pieces behind k-step 1 alone, which every wave has: the waits hold for both
+  // kinds of wave as they stand (copies complete in order; a wave without the piece just has nothing older to wait for)
+  constexpr bool EVEN = 24 % NWAVE == 0;
+  static_assert(EVEN || (L == 2 && NB1 == NB - 1 && NWAVE * NB1 <= 24), "uneven deal: the odd piece goes behind k-step 0, lead 2");
   char* const Abuf = smem;                       // [4][BM rows][32 bytes: the two 16-byte halves swapped on odd groups of 8 rows]
   char* const Bbuf = smem + 4 * U8P_A;           // [L][3 terms][128 columns][64 B swizzled] = the weight image of a slab
   int tm, tn;
@@ -285,11 +297,19 @@ __global__ __launch_bounds__(NWR * 128) __attribute__((amdgpu_waves_per_eu(2, 2)
   const unsigned char* const asrc = x + arow_g * ldx + ((cphys ^ ((crow >> 3) & 1)) << 4);
   const rsrc_t rB = make_rsrc(img + (size_t)tn * nslab * (3 * 128 * 32), 0x7FFFFFFFu);
   const unsigned voffb = (unsigned)lane * 16u;
+  const unsigned char* anext = asrc;             // four waves per SIMD: slabs are issued in order, one running pointer (asrc + s * U8_BK
+                                                 // keeps asrc in two more registers across the slab loop for the last slabs: a spill)
   auto issue_a = [&](int s) {
-    __builtin_amdgcn_global_load_lds((u8p_glb_t)(asrc + (size_t)s * U8_BK), (u8p_lds_t)(Abuf + (s & 3) * U8P_A + wave * 1024), 16, 0, 0);
+    if constexpr (u8p_waves(NWR) == 4) {
+      __builtin_amdgcn_global_load_lds((u8p_glb_t)anext, (u8p_lds_t)(Abuf + (s & 3) * U8P_A + wave * 1024), 16, 0, 0);
+      anext += U8_BK;
+    } else {
+      __builtin_amdgcn_global_load_lds((u8p_glb_t)(asrc + (size_t)s * U8_BK), (u8p_lds_t)(Abuf + (s & 3) * U8P_A + wave * 1024), 16, 0, 0);
+    }
   };
   auto issue_b = [&](int s, int q) {             // piece wave + NWAVE q of the 24
     const int idx = wave + NWAVE * q;
+    if (!EVEN && idx >= 24) return;              // wave-uniform
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rB, (u8p_lds_t)(Bbuf + (s % L) * U8P_B + idx * 1024), 16, voffb,
                                              (unsigned)s * (unsigned)U8P_B + idx * 1024, 0, 0);
   };
@@ -393,8 +413,12 @@ __global__ __launch_bounds__(NWR * 128) __attribute__((amdgpu_waves_per_eu(2, 2)
     kstep(S0, T, F, F, i); kstep(S1, T, F, F, i); ++i;
     kstep(S0, F, F, F, i); kstep(S1, F, F, F, i);
   }
-  // epilogue: as u8_gemm_kernel<true>
-  const int n = n0 + wc * 32 + l31;
+  // epilogue: as u8_gemm_kernel<true>.  At four waves per SIMD (128 registers) the lane's roles are taken from the thread id again
+  // rather than held in four registers across the slab loop, which would spill there
+  int etid = tid;
+  if constexpr (u8p_waves(NWR) == 4) asm volatile("" : "+v"(etid));
+  const int elane = etid & 63, el31 = elane & 31, elh = elane >> 5;
+  const int n = n0 + wc * 32 + el31;
   const bool nok = n < N;
   const bool timg = tsink.img != nullptr;
   if (nok || timg) {
@@ -406,7 +430,7 @@ __global__ __launch_bounds__(NWR * 128) __attribute__((amdgpu_waves_per_eu(2, 2)
       float ov[16];
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int m = m0 + wr * 64 + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+        const int m = m0 + wr * 64 + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * elh;
         const float h = fmaf(acc[mt][0][r], x_scale, vbh);
         const float sg = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-kLog2e * fmaf(acc[mt][1][r], x_scale, vbg)));
         ov[r] = h * sg;
@@ -416,7 +440,7 @@ __global__ __launch_bounds__(NWR * 128) __attribute__((amdgpu_waves_per_eu(2, 2)
           if (save_s) save_s[o] = sg;
         }
       }
-      if (timg) p6_emit_tile(tsink, tsink.row0 + n, nok, tsink.kbase + m0 + wr * 64 + mt * 32, ov, lh);
+      if (timg) p6_emit_tile(tsink, tsink.row0 + n, nok, tsink.kbase + m0 + wr * 64 + mt * 32, ov, elh);
     }
   }
 }
@@ -525,6 +549,25 @@ extern "C" int evae_dense_u8_prepare(const float* wh, const float* wg, int N, in
   return check_launch("u8_prepare_kernel");
 }
 
+// CUs of the current device (the block-height rule counts rounds of blocks in them), asked once per device
+static int u8_device_cus() {
+  static int cached[64] = {0};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { (void)hipGetLastError(); return 256; }
+  if (!cached[dev]) {
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) { (void)hipGetLastError(); cus = 256; }
+    cached[dev] = cus;
+  }
+  return cached[dev];
+}
+
+// rows per block of the copy-pipeline forward at (M, N) on a machine of `cus` CUs (cus <= 0: the current device's)
+extern "C" int evae_dense_u8_block_rows(int M, int N, int cus) {
+  if (M <= 0 || N <= 0) return 128;
+  return u8_fwd_block_rows(M, cdiv(N, U8_BN), cus > 0 ? cus : u8_device_cus());
+}
+
 static int gated_dense_fwd_u8_core(const unsigned char* x, const int64_t* rows, int M, int K, long long ldx, float x_scale,
                                    const void* prepared, const float* bh, const float* bg, int N, float* out,
                                    float* save_s, const P6Sink& tsink, evae_stream_t stream_) {
@@ -543,17 +586,24 @@ static int gated_dense_fwd_u8_core(const unsigned char* x, const int64_t* rows, 
   if (pipe < 0) {
     const char* e = getenv("EVAE_U8_PIPE");
     pipe = e ? atoi(e) : 1;                    // 0: never, 1: machine-filling launches, 2: whenever the contraction allows
-    const char* t = getenv("EVAE_U8_TALL");
+    const char* t = getenv("EVAE_U8_TALL");    // 0: 128-row blocks, 1: u8_fwd_block_rows (evae_tile_map.h), 2: 256 rows, 3: 448 rows
     tall = t ? atoi(t) : 1;
     (void)hipFuncSetAttribute((const void*)u8p_gemm_kernel<2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, u8p_lds_bytes(2, 2));
     (void)hipFuncSetAttribute((const void*)u8p_gemm_kernel<4, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, u8p_lds_bytes(4, 2));
+    (void)hipFuncSetAttribute((const void*)u8p_gemm_kernel<7, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, u8p_lds_bytes(7, 2));
   }
   if (pipe && u8_nslab(K) >= 3 && (pipe == 2 || tiles_m * tiles_n >= 256)) {
-    // a machine-filling launch: the copy-pipeline form of the same kernel; 256-row blocks when those still fill the machine
-    const int tiles_m4 = cdiv(M, 256);
-    if (tall && (tall == 2 || tiles_m4 * tiles_n >= 256)) {
-      u8p_gemm_kernel<4, 2><<<tile_grid(tiles_m4 * tiles_n), 512, u8p_lds_bytes(4, 2), (hipStream_t)stream_>>>(
-          x, rows, M, ldx, x_scale, (const unsigned short*)prepared, u8_nslab(K), bh, bg, N, out, save_s, tiles_m4, tiles_n, tsink);
+    // a machine-filling launch: the copy-pipeline form of the same kernel, at the block height that fits the machine
+    const int bm = tall == 1 ? u8_fwd_block_rows(M, tiles_n, u8_device_cus()) : tall == 2 ? 256 : tall == 3 ? 448 : 128;
+    const int tiles_mb = cdiv(M, bm);
+    if (bm == 448) {
+      u8p_gemm_kernel<7, 2><<<tile_grid(tiles_mb * tiles_n), 896, u8p_lds_bytes(7, 2), (hipStream_t)stream_>>>(
+          x, rows, M, ldx, x_scale, (const unsigned short*)prepared, u8_nslab(K), bh, bg, N, out, save_s, tiles_mb, tiles_n, tsink);
+      return check_launch("u8p_gemm_kernel<7, 2>");
+    }
+    if (bm == 256) {
+      u8p_gemm_kernel<4, 2><<<tile_grid(tiles_mb * tiles_n), 512, u8p_lds_bytes(4, 2), (hipStream_t)stream_>>>(
+          x, rows, M, ldx, x_scale, (const unsigned short*)prepared, u8_nslab(K), bh, bg, N, out, save_s, tiles_mb, tiles_n, tsink);
       return check_launch("u8p_gemm_kernel<4, 2>");
     }
     u8p_gemm_kernel<2, 2><<<tile_grid(tiles_m * tiles_n), 256, u8p_lds_bytes(2, 2), (hipStream_t)stream_>>>(

@@ -34,6 +34,22 @@ EVAE_HD_INLINE int tile_of_block(const BlockPlace b, const int ntiles) {
 EVAE_HD_INLINE int tile_of_block(const int id, const int ntiles) { return tile_of_block(block_place(id), ntiles); }
 inline int tile_grid(const int ntiles) { return ntiles; }
 
+// ---- block height of the byte layer's copy-pipeline forward (u8p_gemm_kernel, evae_dense_u8.hip): rows per block, 128, 256 or
+// 448, for M rows x tiles_n column tiles on cus CUs.  The 256- and 448-row blocks run one per CU, so a launch takes
+// ceil(blocks / cus) rounds and its busiest CU works through rounds x height rows.  256 rows (half the weight-image bytes per row
+// of 128) once those blocks still fill the machine; 448 where they get the busiest CU through fewer rounds AND fewer rows --
+// 19 968 rows x 5 tiles on 256 CUs: 225 blocks, one round of 448 rows, against 390 blocks, two rounds = 512 rows; at 25 000 rows
+// both heights take two rounds and the launch stays at 256.
+inline int u8_fwd_rounds(const int M, const int tiles_n, const int cus, const int h) {
+  const int blocks = ((M + h - 1) / h) * tiles_n;
+  return (blocks + cus - 1) / cus;
+}
+inline int u8_fwd_block_rows(const int M, const int tiles_n, const int cus) {
+  if (((M + 255) / 256) * tiles_n < cus) return 128;
+  const int r256 = u8_fwd_rounds(M, tiles_n, cus, 256), r448 = u8_fwd_rounds(M, tiles_n, cus, 448);
+  return (r448 < r256 && r448 * 448 < r256 * 256) ? 448 : 256;
+}
+
 // ---- units (the XCD-local split-K): a UNIT is a set of `per_unit` blocks that read the same heavy operand strip -- the tiles
 // of one (contraction slice, row or column tile) along the other tile axis; the call site says which operand.  A unit sits on
 // ONE XCD, dispatched back to back, so its blocks walk the slice in step and all but the first find every slab in that XCD's

@@ -116,6 +116,7 @@ SIGNATURES = {
     "evae_dense_bwd_weight": (_i, [_p, _i, _i, _i, _p, _p, _i, _i, _p, _p, _i, _p, _z, _p]),
     "evae_dense_bwd_weight_phased": (_i, [_p, _i, _i, _i, _p, _p, _i, _i, _p, _p, _i, _p, _z, _i, _p]),
     "evae_dense_u8_supported": (_i, [_i, C.c_longlong]),
+    "evae_dense_u8_block_rows": (_i, [_i, _i, _i]),
     "evae_dense_u8_prepared_bytes": (_z, [_i, _i]),
     "evae_dense_u8_prepare": (_i, [_p, _p, _i, _i, _p, _z, _p]),
     "evae_gated_dense_fwd_u8": (_i, [_p, _p, _i, _i, C.c_longlong, _f, _p, _p, _p, _i, _p, _p, _p]),

@@ -386,6 +386,9 @@ int evae_dense_u8_prepare(const float* wh, const float* wg, int N, int K, void* 
 int evae_gated_dense_fwd_u8(const unsigned char* x, const int64_t* rows, int M, int K, long long ldx, float x_scale,
                             const void* prepared, const float* bh, const float* bg, int N,
                             float* out /* [M x N] */, float* save_s /* [M x N] or NULL */, evae_stream_t stream);
+/* Rows per block (128, 256 or 448) that a machine-filling forward launch of M rows x N outputs takes on a device of `cus` CUs
+ * (cus <= 0: the current device's): the host rule u8_fwd_block_rows of csrc/evae_tile_map.h, for tests and tools. */
+int evae_dense_u8_block_rows(int M, int N, int cus);
 /* Weight gradient of that layer: dw [N x K] = x_scale * dy^T x(rows), db [N] = column sums of dy (dy [M x N], row stride ldy:
  * the merged [dh | dg] buffer).  Same arithmetic: the byte rows are exact in bf16, dy is split exactly into three bf16 terms;
  * pre-passes transpose the gathered bytes and lay dy^T out in tile order, the product runs split along the batch rows into
