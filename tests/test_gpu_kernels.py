@@ -664,6 +664,180 @@ def test_adam_normgrad_ragged_sizes_vs_oracle(ops):
                 assert rel(vs[i].cpu().numpy(), v_np[i]) < 1e-5, (sizes[i], step)
 
 
+def _adam_carve(sizes, unaligned):
+    """The four tensors (param, grad, exp_avg, exp_avg_sq) of every size as views of ONE flat NaN-filled buffer: a view starts on
+    a 16-byte boundary, or one float behind one where `unaligned` names its kind, and at least three NaN guard floats lie
+    between two views.  -> (buffer, guard mask, [four lists of views])"""
+    kinds = ("param", "grad", "exp_avg", "exp_avg_sq")
+    spans, off = [], 4
+    for n in sizes:
+        for kind in kinds:
+            start = off + (1 if kind in unaligned else 0)
+            spans.append((start, n))
+            off = (start + n + 3 + 3) // 4 * 4
+    buf = torch.full((off + 4,), float("nan"), device="cuda")
+    assert buf.data_ptr() % 16 == 0
+    guard = torch.ones(buf.numel(), dtype=torch.bool, device="cuda")
+    views = [[], [], [], []]
+    for j, (start, n) in enumerate(spans):
+        v = buf[start:start + n]
+        assert (v.data_ptr() % 16 != 0) == (kinds[j % 4] in unaligned)
+        guard[start:start + n] = False
+        views[j % 4].append(v)
+    return buf, guard, views
+
+
+def _adam_check(sizes, ps, ms, vs, p_np, m_np, v_np, tag):
+    for i in range(len(sizes)):
+        assert rel(ps[i].cpu().numpy(), p_np[i]) < 1e-6, (sizes[i], tag)
+        assert rel(ms[i].cpu().numpy(), m_np[i]) < 1e-5, (sizes[i], tag)
+        assert rel(vs[i].cpu().numpy(), v_np[i]) < 1e-5, (sizes[i], tag)
+
+
+@pytest.mark.parametrize("unaligned", [("param", "grad", "exp_avg", "exp_avg_sq"), ("grad",), ("param",)])
+def test_adam_normgrad_unaligned_views_take_the_scalar_path(ops, unaligned):
+    """adam_sumsq_kernel reads float4 only from a 16-byte aligned gradient, adam_step_kernel only when all four pointers are
+    aligned: views one float off a boundary run the scalar loops.  Three steps (the second with weight decay) against the
+    oracle; the guard floats between the views stay NaN."""
+    rs = np.random.RandomState(31)
+    sizes = [1, 5, 2049, 262147]
+    buf, guard, (ps, gs, ms, vs) = _adam_carve(sizes, unaligned)
+    p_np = [rs.standard_normal(n).astype(np.float32) for n in sizes]
+    m_np = [np.zeros(n, np.float32) for n in sizes]; v_np = [np.zeros(n, np.float32) for n in sizes]
+    for i in range(len(sizes)):
+        ps[i].copy_(dev(p_np[i])); ms[i].zero_(); vs[i].zero_()
+    for step, wd in ((1, 0.0), (2, 1e-3), (3, 0.0)):
+        g_np = [(rs.standard_normal(n) * 10.0 ** rs.uniform(-3, 1)).astype(np.float32) for n in sizes]
+        for i in range(len(sizes)):
+            gs[i].copy_(dev(g_np[i]))
+        ops.adam_normgrad_step(ps, gs, ms, vs, step, 5e-4, 0.9, 0.999, 1e-8, wd)
+        for i in range(len(sizes)):
+            p_np[i], m_np[i], v_np[i] = orc.adam_normgrad_step(p_np[i], g_np[i], m_np[i], v_np[i], step, weight_decay=wd)
+            assert np.array_equal(gs[i].cpu().numpy(), g_np[i])                      # the gradient is read, never written
+        _adam_check(sizes, ps, ms, vs, p_np, m_np, v_np, (unaligned, step))
+        assert bool(torch.isnan(buf[guard]).all()), (unaligned, step)
+        assert int(guard.sum()) >= 3 * 4 * len(sizes)
+
+
+def test_adam_normgrad_chunk_boundaries(ops):
+    """Tensors of exactly ANB * ACHUNK = 128 * 2048 elements (128 blocks of the smallest chunk), one more (chunks of 3072), exactly
+    128 * 3072 and one more (chunks of 4096), in one call with a 1-element tensor (whose blocks past the first return at once)."""
+    rs = np.random.RandomState(32)
+    sizes = [262144, 262145, 1, 393216, 393217]
+    p_np = [rs.standard_normal(n).astype(np.float32) for n in sizes]
+    m_np = [np.zeros(n, np.float32) for n in sizes]; v_np = [np.zeros(n, np.float32) for n in sizes]
+    ps = [dev(a.copy()) for a in p_np]
+    ms = [torch.zeros_like(p) for p in ps]; vs = [torch.zeros_like(p) for p in ps]
+    for step in (1, 2):
+        g_np = [(rs.standard_normal(n) * 10.0 ** rs.uniform(-3, 1)).astype(np.float32) for n in sizes]
+        # the last element of every chunk-aligned tensor carries weight in the norm: a chunk lost at the end would show
+        for g in g_np:
+            g[-1] = 5.0 * np.abs(g).max()
+        ops.adam_normgrad_step(ps, [dev(g) for g in g_np], ms, vs, step, 5e-4, 0.9, 0.999, 1e-8, 0.0)
+        for i in range(len(sizes)):
+            p_np[i], m_np[i], v_np[i] = orc.adam_normgrad_step(p_np[i], g_np[i], m_np[i], v_np[i], step)
+        _adam_check(sizes, ps, ms, vs, p_np, m_np, v_np, step)
+
+
+def test_adam_normgrad_zero_gradient_tensor_among_others(ops):
+    """A tensor whose gradient is all zeros: norm 0, g / (0 + 1e-7) = 0, moments 0, update 0 / (0 + eps) = 0 -- finite, and the
+    parameter stays where it was; the step after, with a real gradient, starts from those zero moments."""
+    rs = np.random.RandomState(33)
+    sizes = [300, 2049, 7]
+    p_np = [rs.standard_normal(n).astype(np.float32) for n in sizes]
+    m_np = [np.zeros(n, np.float32) for n in sizes]; v_np = [np.zeros(n, np.float32) for n in sizes]
+    ps = [dev(a.copy()) for a in p_np]
+    ms = [torch.zeros_like(p) for p in ps]; vs = [torch.zeros_like(p) for p in ps]
+    for step in (1, 2):
+        g_np = [rs.standard_normal(n).astype(np.float32) for n in sizes]
+        if step == 1:
+            g_np[1][:] = 0.0
+        ops.adam_normgrad_step(ps, [dev(g) for g in g_np], ms, vs, step, 5e-4, 0.9, 0.999, 1e-8, 0.0)
+        for t in ps + ms + vs:
+            assert bool(torch.isfinite(t).all()), step
+        if step == 1:
+            assert np.array_equal(ps[1].cpu().numpy(), p_np[1])
+            assert not bool(ms[1].any()) and not bool(vs[1].any())
+        for i in range(len(sizes)):
+            p_np[i], m_np[i], v_np[i] = orc.adam_normgrad_step(p_np[i], g_np[i], m_np[i], v_np[i], step)
+        _adam_check(sizes, ps, ms, vs, p_np, m_np, v_np, step)
+
+
+def test_adam_normgrad_two_hundred_small_tensors_in_one_call(ops):
+    rs = np.random.RandomState(34)
+    sizes = list(range(1, 201))
+    p_np = [rs.standard_normal(n).astype(np.float32) for n in sizes]
+    m_np = [np.zeros(n, np.float32) for n in sizes]; v_np = [np.zeros(n, np.float32) for n in sizes]
+    flat = lambda arrs: dev(np.concatenate(arrs))
+    split = lambda t: list(torch.split(t, sizes))
+    P, M, V = flat(p_np), torch.zeros(sum(sizes), device="cuda"), torch.zeros(sum(sizes), device="cuda")
+    for step in (1, 2):
+        g_np = [(rs.standard_normal(n) * 10.0 ** rs.uniform(-3, 1)).astype(np.float32) for n in sizes]
+        ops.adam_normgrad_step(split(P), split(flat(g_np)), split(M), split(V), step, 5e-4, 0.9, 0.999, 1e-8, 0.0)
+        for i in range(len(sizes)):
+            p_np[i], m_np[i], v_np[i] = orc.adam_normgrad_step(p_np[i], g_np[i], m_np[i], v_np[i], step)
+        got = [np.split(t.cpu().numpy(), np.cumsum(sizes)[:-1]) for t in (P, M, V)]
+        for i in range(len(sizes)):
+            assert rel(got[0][i], p_np[i]) < 1e-6, (sizes[i], step)
+            assert rel(got[1][i], m_np[i]) < 1e-5, (sizes[i], step)
+            assert rel(got[2][i], v_np[i]) < 1e-5, (sizes[i], step)
+
+
+def _adam_state(rs, sizes):
+    ps = [dev(rs.standard_normal(n).astype(np.float32)) for n in sizes]
+    return ps, [torch.zeros_like(p) for p in ps], [torch.zeros_like(p) for p in ps]
+
+
+def test_adam_normgrad_step_size_from_device_memory(ops):
+    """step_size_dev: the captured step's bias-corrected step size read from a device scalar -- `lr` is then not used at all"""
+    import math
+    sizes = [1, 7, 2049, 300 * 40]
+    grads = [[dev((np.random.RandomState(40 + s).standard_normal(n)).astype(np.float32)) for n in sizes] for s in range(3)]
+    a = _adam_state(np.random.RandomState(35), sizes)
+    b = _adam_state(np.random.RandomState(35), sizes)
+    for step in (1, 2, 3):
+        ops.adam_normgrad_step(a[0], grads[step - 1], a[1], a[2], step, 5e-4, 0.9, 0.999, 1e-8, 0.0)
+        ss = torch.tensor([5e-4 * math.sqrt(1.0 - 0.999 ** step) / (1.0 - 0.9 ** step)], dtype=torch.float32, device="cuda")
+        ops.adam_normgrad_step(b[0], grads[step - 1], b[1], b[2], step, 123.0, 0.9, 0.999, 1e-8, 0.0, step_size_dev=ss)
+        for x, y in zip(a[0] + a[1] + a[2], b[0] + b[1] + b[2]):
+            assert torch.equal(x, y), step
+
+
+def test_adam_normgrad_with_the_step_statistics_in_its_last_launch(ops):
+    """evae_adam_normgrad_step_stats, the launch that ends a captured step: the update is the plain call's bit for bit, step3 =
+    (loss, -re, kl), totals3 += step3 in float32, the parity word flips with every call; totals3 and the parity word may be absent."""
+    sizes = [1, 7, 2049, 128 * 2048 + 5]
+    grads = [[dev((np.random.RandomState(50 + s).standard_normal(n)).astype(np.float32)) for n in sizes] for s in range(4)]
+    vals = np.random.RandomState(36).normal(0.0, 50.0, (4, 3)).astype(np.float32)
+    a = _adam_state(np.random.RandomState(37), sizes)
+    b = _adam_state(np.random.RandomState(37), sizes)
+    step3 = torch.full((4,), float("nan"), device="cuda")
+    totals = torch.zeros(4, device="cuda"); totals[3] = float("nan")
+    toggle = torch.zeros(2, dtype=torch.int32, device="cuda"); toggle[1] = 77
+    want = np.zeros(3, np.float32)
+    assert toggle.cpu().tolist() == [0, 77]
+    for k in range(3):
+        step = k + 1
+        loss, re, kl = (dev(vals[k, j:j + 1]) for j in range(3))
+        ops.adam_normgrad_step(a[0], grads[k], a[1], a[2], step, 5e-4, 0.9, 0.999, 1e-8, 0.0)
+        ops.adam_normgrad_step(b[0], grads[k], b[1], b[2], step, 5e-4, 0.9, 0.999, 1e-8, 0.0, stats=(loss, re, kl, step3, totals, toggle))
+        for x, y in zip(a[0] + a[1] + a[2], b[0] + b[1] + b[2]):
+            assert torch.equal(x, y), step
+        now = np.array([vals[k, 0], -vals[k, 1], vals[k, 2]], np.float32)
+        want = want + now
+        assert np.array_equal(step3[:3].cpu().numpy(), now) and bool(torch.isnan(step3[3]))
+        assert np.array_equal(totals[:3].cpu().numpy(), want) and bool(torch.isnan(totals[3]))
+        assert toggle.cpu().tolist() == [(k + 1) & 1, 77]
+    # without the running sums and without the parity word
+    loss, re, kl = (dev(vals[3, j:j + 1]) for j in range(3))
+    ops.adam_normgrad_step(a[0], grads[3], a[1], a[2], 4, 5e-4, 0.9, 0.999, 1e-8, 0.0)
+    ops.adam_normgrad_step(b[0], grads[3], b[1], b[2], 4, 5e-4, 0.9, 0.999, 1e-8, 0.0, stats=(loss, re, kl, step3, None, None))
+    for x, y in zip(a[0] + a[1] + a[2], b[0] + b[1] + b[2]):
+        assert torch.equal(x, y)
+    assert np.array_equal(step3[:3].cpu().numpy(), np.array([vals[3, 0], -vals[3, 1], vals[3, 2]], np.float32))
+    assert np.array_equal(totals[:3].cpu().numpy(), want) and toggle.cpu().tolist() == [1, 77]
+
+
 def test_fused_elementwise_backward_launches_match_their_parts():
     """evae_bernoulli_sigmoid_bwd == evae_bernoulli_ll_bwd then evae_act_bwd(sigmoid);
     evae_reparam_logq_bwd_hardtanh == (dz + dz2) -> evae_reparam_logq_bwd -> evae_act_bwd(hardtanh)."""
