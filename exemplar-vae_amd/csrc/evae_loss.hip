@@ -4,6 +4,7 @@
 #include "evae_common.h"
 #include "evae_u8_prepare.h"
 #include "evae_p6_image.h"
+#include "evae_philox.h"
 
 namespace evae {
 
@@ -400,19 +401,7 @@ __global__ __launch_bounds__(256) void reparam_logq_bwd_ht_tail_kernel(
 // ---- head of a training step: batch gather + dynamic binarisation + eps, one launch ---------------------------------
 // Counter-based generator (Philox4x32-10): element e of stream s at step t always gets the same 128 random bits for a
 // given seed, whatever the launch geometry -- a replayed hipGraph only needs the step counter in device memory.
-__device__ __forceinline__ uint4 philox4x32(uint4 c, uint2 k) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c.x), lo0 = 0xD2511F53u * c.x;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c.z), lo1 = 0xCD9E8D57u * c.z;
-    c = make_uint4(hi1 ^ c.y ^ k.x, lo1, hi0 ^ c.w ^ k.y, lo0);
-    k.x += 0x9E3779B9u;
-    k.y += 0xBB67AE85u;
-  }
-  return c;
-}
-__device__ __forceinline__ float u01(uint32_t r) { return (float)(r >> 8) * 5.9604644775390625e-8f; }          // [0, 1)
-__device__ __forceinline__ float u01_open(uint32_t r) { return (float)((r >> 8) + 1u) * 5.9604644775390625e-8f; }  // (0, 1]
+// (evae_philox.h: philox4x32, u01, u01_open)
 
 __global__ __launch_bounds__(256) void batch_prologue_kernel(const float* __restrict__ data, int64_t ldd,
                                                              const int64_t* __restrict__ idx, int B, int D, int binarize,

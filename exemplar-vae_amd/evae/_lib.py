@@ -17,6 +17,7 @@ _d = C.c_double
 _z = C.c_size_t
 _l = C.c_int64
 _u = C.c_uint
+_q = C.c_uint64
 
 
 class ConvDesc(C.Structure):
@@ -162,6 +163,14 @@ SIGNATURES = {
     "evae_gemm_x6_configure": (_i, [_i, _i]),
     "evae_gemm_x6_applies": (_i, [_i, _i, _i]),
     "evae_elu_fwd": (_i, [_p, _z, _p, _p]),
+    "evae_causal_attn_max_len": (_i, []),
+    "evae_causal_attn_lds_bytes": (_z, [_i, _i]),
+    "evae_causal_attn_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _f, _q, _q, _p, _p, _p]),
+    "evae_causal_attn_bwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _q, _q, _p, _p, _p, _p, _p]),
+    "evae_elu_dropout_fwd": (_i, [_p, _z, _f, _q, _q, _p, _p]),
+    "evae_elu_dropout_bwd": (_i, [_p, _p, _z, _f, _q, _q, _p, _p]),
+    "evae_glu_res_fwd": (_i, [_p, _p, _l, _i, _p, _p]),
+    "evae_glu_res_bwd": (_i, [_p, _p, _l, _i, _p, _p]),
     "evae_conv2d_cl_res_supported": (_i, [_p]),
     "evae_conv2d_cl_fwd_res": (_i, [_p, _p, _p, _p, _p, _p, _p, _z, _p]),
     "evae_conv2d_cl_bwd_data_res": (_i, [_p, _p, _p, _p, _p, _p, _p, _z, _p]),

@@ -2432,3 +2432,142 @@ def adam_normgrad_step(params, grads, exp_avgs, exp_avg_sqs, step, lr, beta1, be
                                            float(beta1), float(beta2), float(eps), float(weight_decay),
                                            _p(step_size_dev), _p(ws), ws.numel(), _stream()),
                "evae_adam_normgrad_step")
+
+
+# ------------------------------------------------------------------------------------------------
+# PixelSNAIL decoder (utils/nn.py: CausalAttention, GatedResBlock): csrc/evae_attn.hip
+# ------------------------------------------------------------------------------------------------
+_DROPOUT_CALLS = [0]
+
+
+def dropout_rng():
+    """(seed, offset) of the next dropout mask: the seed of torch.manual_seed, and a per-process counter that every dropout call
+    advances (it is the high half of the Philox counter, so no two calls of a process share a mask)."""
+    off = _DROPOUT_CALLS[0]
+    _DROPOUT_CALLS[0] = off + 1
+    return int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF, off
+
+
+def _rng_args(p_drop, rng):
+    """p_drop = 0 draws nothing (and leaves the counter alone)"""
+    p_drop = float(p_drop)
+    if p_drop == 0.0:
+        return 0.0, 0, 0
+    seed, offset = dropout_rng() if rng is None else rng
+    return p_drop, int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFFFFFFFFFF
+
+
+def causal_attn_max_len():
+    return int(_lib.load().evae_causal_attn_max_len())
+
+
+class CausalAttnFn(torch.autograd.Function):
+    """Causal attention of reference utils/nn.py:351-359 on projected rows: q, k, v [B*L, H*dh] -> out [B*L, H*dh].  Saves q, k, v,
+    out and one log-sum-exp per row; the dropout mask is regenerated from (seed, offset) in the backward pass."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, B, L, H, p_drop, seed, offset):
+        lib = _lib.load()
+        _need_cuda(q, k, v)
+        q, k, v = _f32(q), _f32(k), _f32(v)
+        if not (q.dim() == 2 and q.shape == k.shape == v.shape and q.shape[0] == B * L and q.shape[1] % H == 0):
+            raise _lib.EvaeError("causal_attn: q, k, v must be [B*L, H*dh] rows of one shape")
+        dh = q.shape[1] // H
+        out = torch.empty_like(q)
+        lse = torch.empty((B, H, L), device=q.device)
+        _lib.check(lib.evae_causal_attn_fwd(_p(q), _p(k), _p(v), B, H, L, dh, p_drop, seed, offset, _p(out), _p(lse), _stream()),
+                   "evae_causal_attn_fwd")
+        ctx.save_for_backward(q, k, v, out, lse)
+        ctx.cfg = (B, L, H, dh, p_drop, seed, offset)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = _lib.load()
+        q, k, v, out, lse = ctx.saved_tensors
+        B, L, H, dh, p_drop, seed, offset = ctx.cfg
+        dout = _f32(dout)
+        dq, dk, dv = torch.empty_like(q), torch.empty_like(q), torch.empty_like(q)
+        delta = torch.empty_like(lse)                # scratch: the row pass hands delta_i to the column pass
+        _lib.check(lib.evae_causal_attn_bwd(_p(q), _p(k), _p(v), _p(out), _p(lse), _p(dout), B, H, L, dh, p_drop, seed, offset,
+                                            _p(delta), _p(dq), _p(dk), _p(dv), _stream()), "evae_causal_attn_bwd")
+        return dq, dk, dv, None, None, None, None, None, None
+
+
+def causal_attn(q, k, v, B, L, H, p_drop=0.0, rng=None):
+    """rng = (seed, offset): an explicit mask (tests); None: dropout_rng()"""
+    return CausalAttnFn.apply(q, k, v, int(B), int(L), int(H), *_rng_args(p_drop, rng))
+
+
+def _dense(t):
+    """a tensor whose storage is one dense block (any permutation of a contiguous tensor: NCHW or channels-last)"""
+    if t.is_contiguous() or (t.dim() == 4 and t.is_contiguous(memory_format=CL)):
+        return t
+    return t.contiguous()
+
+
+class EluDropoutFn(torch.autograd.Function):
+    """dropout(ELU(x)) in one launch, the mask over the flat storage index; the output keeps x's layout"""
+
+    @staticmethod
+    def forward(ctx, x, p_drop, seed, offset):
+        lib = _lib.load()
+        _need_cuda(x)
+        x = _dense(x.float())
+        out = torch.empty_like(x)                    # (preserve_format: the same strides)
+        _lib.check(lib.evae_elu_dropout_fwd(_p(x), x.numel(), p_drop, seed, offset, _p(out), _stream()), "evae_elu_dropout_fwd")
+        ctx.save_for_backward(x)
+        ctx.cfg = (p_drop, seed, offset)
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = _lib.load()
+        x, = ctx.saved_tensors
+        dy = dy.float()
+        if dy.stride() != x.stride():
+            dy = torch.empty_like(x).copy_(dy)
+        dx = torch.empty_like(x)
+        _lib.check(lib.evae_elu_dropout_bwd(_p(dy), _p(x), x.numel(), *ctx.cfg, _p(dx), _stream()), "evae_elu_dropout_bwd")
+        return dx, None, None, None
+
+
+def elu_dropout(x, p_drop=0.0, rng=None):
+    return EluDropoutFn.apply(x, *_rng_args(p_drop, rng))
+
+
+class GluResFn(torch.autograd.Function):
+    """a * sigmoid(b) + x with (a, b) the channel halves of `ab` (nn.GLU(1) + the residual of GatedResBlock): ab [N, 2C, H, W] and
+    x [N, C, H, W] as channels-last tensors (or [M, 2C] and [M, C] rows); the output has x's shape, channels-last."""
+
+    @staticmethod
+    def forward(ctx, ab, x):
+        lib = _lib.load()
+        _need_cuda(ab, x)
+        if ab.dim() == 4:
+            ab, x = _cl(ab.float()), _cl(x.float())
+            M, Cc = x.shape[0] * x.shape[2] * x.shape[3], x.shape[1]
+        else:
+            ab, x = _f32(ab), _f32(x)
+            M, Cc = x.shape
+        if ab.shape[1] != 2 * Cc or ab.numel() != 2 * x.numel():
+            raise _lib.EvaeError("glu_res: ab must have twice the channels of x")
+        out = torch.empty_like(x)
+        _lib.check(lib.evae_glu_res_fwd(_p(ab), _p(x), M, Cc, _p(out), _stream()), "evae_glu_res_fwd")
+        ctx.save_for_backward(ab)
+        ctx.cfg = (M, Cc)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = _lib.load()
+        ab, = ctx.saved_tensors
+        M, Cc = ctx.cfg
+        dout = _cl(dout.float()) if ab.dim() == 4 else _f32(dout)
+        dab = torch.empty_like(ab)
+        _lib.check(lib.evae_glu_res_bwd(_p(dout), _p(ab), M, Cc, _p(dab), _stream()), "evae_glu_res_bwd")
+        return dab, dout
+
+
+def glu_res(ab, x):
+    return GluResFn.apply(ab, x)

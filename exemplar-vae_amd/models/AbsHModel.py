@@ -1,5 +1,5 @@
 """Two-latent-layer VAE (z2 under the exemplar prior, z1 | z2 Gaussian): composition of the sub-networks a concrete
-model declares (models.HVAE_2level, models.convHVAE_2level).  Behavioural contract: reference
+model declares (models.HVAE_2level, models.convHVAE_2level, models.PixelCNN -- whose decoder also reads x).  Behavioural contract: reference
 models/AbsHModel.py:8-107 -- method names, argument order, the 8-tuple of latent statistics and the flat
 [B x D] decoder outputs are what models.BaseModel and utils.evaluation rely on."""
 import os
@@ -33,6 +33,9 @@ class BaseHModel(BaseModel):
     def _is_conv_hvae(self):
         return 'convhvae_2level' in self.args.model_name
 
+    def _is_pixelcnn(self):
+        return self.args.model_name == 'pixelcnn'
+
     # ---- conditionals ----------------------------------------------------------------------------------------------
     def p_z1(self, z2):
         """p(z1 | z2): mean, log-variance"""
@@ -42,13 +45,18 @@ class BaseHModel(BaseModel):
     def q_z1(self, x, z2):
         """q(z1 | x, z2): the image branch and the z2 branch are concatenated before the joint layer"""
         img = self.q_z1_layers_x(x)
-        if self.args.model_name == 'convhvae_2level':
+        if self.args.model_name == 'convhvae_2level' or self._is_pixelcnn():
             img = img.reshape(img.size(0), -1)   # conv features may be channels-last tensors: reshape keeps (c, y, x) order
         joint = self.q_z1_layers_joint(torch.cat((img, self.q_z1_layers_z2(z2)), dim=1))
         return self.q_z1_mean(joint), self.q_z1_logvar(joint)
 
     def p_x(self, z1, z2, x=None):
-        """p(x | z1, z2) -> (mean, log-variance); log-variance is the scalar 0 for binary data"""
+        """p(x | z1, z2) -> (mean, log-variance); log-variance is the scalar 0 for binary data.  pixelcnn: p(x | z1, z2, x), the
+        autoregressive decoder over (x, image(z1), image(z2)) (reference models/AbsHModel.py:67-72, binary inputs)"""
+        if self._is_pixelcnn():
+            shape = (-1,) + tuple(self.args.input_size)
+            h = torch.cat((x.view(shape), self.p_x_layers_z1(z1).view(shape), self.p_x_layers_z2(z2).view(shape)), 1)
+            return self.p_x_mean(self.pixelcnn(h)).reshape(-1, int(np.prod(self.args.input_size))), 0.
         feat = torch.cat((self.p_x_layers_z1(z1), self.p_x_layers_z2(z2)), dim=1)
         conv, D = self._is_conv_hvae(), int(np.prod(self.args.input_size))
         if conv:                                   # dense pre-layer -> image -> gated conv stack
@@ -64,6 +72,8 @@ class BaseHModel(BaseModel):
     def generate_x_from_z(self, z, with_reparameterize=True):
         mu1, lv1 = self.p_z1(z)
         z1 = self.reparameterize(mu1, lv1) if with_reparameterize else mu1
+        if self._is_pixelcnn():
+            return self.pixelcnn_generate(z1.view(-1, self.args.z1_size), z.reshape(-1, self.args.z2_size))
         return self.p_x(z1.view(-1, self.args.z1_size), z.view(-1, self.args.z2_size))[0]
 
     # ---- objective -------------------------------------------------------------------------------------------------
@@ -114,7 +124,8 @@ class BaseHModel(BaseModel):
         a = self.args
         return (_TWO_STREAM and self.training and a.prior == 'exemplar_prior' and a.approximate_prior is False
                 and exemplars_embedding is None and dataset is not None and x_indices is not None and x.is_cuda
-                and torch.is_grad_enabled() and (not self._is_conv() or _two_stream_conv()) and not self._sharded())
+                and torch.is_grad_enabled() and (not self._is_conv() or _two_stream_conv()) and not self._sharded()
+                and not self._is_pixelcnn())            # (its decoder reads x: the eager modular path, one stream)
 
     def calculate_loss(self, x, beta=1., average=False, exemplars_embedding=None, cache=None, dataset=None):
         """Training step with the exact exemplar prior on one device (reference models/BaseModel.py:54-77 over AbsHModel.py:13-106):
@@ -177,5 +188,5 @@ class BaseHModel(BaseModel):
         q1_mu, q1_lv = self.q_z1(x, z2)
         z1 = self.reparameterize(q1_mu, q1_lv)
         p1_mu, p1_lv = self.p_z1(z2)
-        mean, logvar = self.p_x(z1, z2)
+        mean, logvar = self.p_x(z1, z2, x=x) if self._is_pixelcnn() else self.p_x(z1, z2)
         return mean, logvar, (z1, q1_mu, q1_lv, z2, q2_mu, q2_lv, p1_mu, p1_lv)

@@ -373,7 +373,9 @@ class BaseModel(nn.Module, ABC):
         return z.reshape(-1, N, pseudo.shape[1])
 
     def reconstruct_x(self, x):
-        x_reconstructed, _, _ = self.forward(x)
+        x_reconstructed, _, z = self.forward(x)
+        if self.args.model_name == 'pixelcnn':              # reference :178-179: sampled from the decoder, not its teacher-forced mean
+            x_reconstructed = self.pixelcnn_generate(z[0].reshape(-1, self.args.z1_size), z[3].reshape(-1, self.args.z2_size))
         return x_reconstructed
 
     def logit_inverse(self, x):
@@ -395,7 +397,7 @@ class BaseModel(nn.Module, ABC):
 
     # ------------------------------------------------------------------ encoder
     def _is_conv(self):
-        return 'conv' in self.args.model_name
+        return 'conv' in self.args.model_name or self.args.model_name == 'pixelcnn'      # (reference :206)
 
     def _encode_rows(self, layers, x, rows=None):
         """Run an encoder stack; for dense stacks `rows` gathers x[rows] inside the first layer's GEMM."""
@@ -430,7 +432,7 @@ class BaseModel(nn.Module, ABC):
         if self._is_conv():
             x = x.view(-1, self.args.input_size[0], self.args.input_size[1], self.args.input_size[2])
         h = self._encode_rows(self.q_z_layers, x, rows)
-        if self.args.model_name == 'convhvae_2level':
+        if self.args.model_name in ('convhvae_2level', 'pixelcnn'):
             h = h.reshape(h.size(0), -1)         # conv outputs may be channels-last tensors
         z_q_mean = self.q_z_mean(h)
         n = h.shape[0]

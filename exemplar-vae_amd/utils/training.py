@@ -86,6 +86,8 @@ def _graphed_step(args, model, optimizer, train_loader):
     if not getattr(args, 'use_hip_graph', True) or not str(args.device).startswith('cuda'):
         return None
     a = model.args
+    if a.model_name == 'pixelcnn':
+        return None        # eager: its dropout masks take their Philox offset from a host counter, which a replay would freeze
     # capturable: the exact exemplar prior, and the approximate (cache + top-k) one on a single device with the leave-one-out
     # mask on -- its exemplar union lives in a fixed list of B * k slots with masked repeats instead of a data-dependent
     # `unique` (models/BaseModel.py::get_approximate_nearest_exemplars; dense encoders only: a convolutional encoder would

@@ -4,13 +4,14 @@ import os
 
 import torch
 
-# model_name -> module that defines the class `VAE`.  'pixelcnn' / 'new_vae' of the reference are outside the
-# accelerated path.
+# model_name -> module that defines the class `VAE`.  'new_vae' of the reference is outside the accelerated path
+# (SURVEY.md section 2).
 _MODEL_MODULES = {
     'vae': 'models.VAE',
     'hvae_2level': 'models.HVAE_2level',
     'convhvae_2level': 'models.convHVAE_2level',
     'single_conv': 'models.fully_conv',
+    'pixelcnn': 'models.PixelCNN',
 }
 
 

@@ -511,6 +511,43 @@ int evae_conv2d_cl_fwd_res(const float* a, const evae_conv_desc_t* d, const floa
 int evae_conv2d_cl_bwd_data_res(const float* dy, const float* w, const evae_conv_desc_t* d, const float* residual,
                                 const float* elu_out, float* dx, void* ws, size_t ws_bytes, evae_stream_t stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * PixelSNAIL decoder (model_name 'pixelcnn'; reference utils/nn.py:253-365), csrc/evae_attn.hip.
+ *
+ * Causal attention behind the three projections (utils/nn.py:339-365): q, k, v, out, dout, dq, dk, dv are rows [B*L, H*dh] with head
+ * h in columns [h dh, (h+1) dh), 16-byte aligned; lse is [B, H, L].
+ *     s_ij = (q_i . k_j) / sqrt(dh), columns j >= i filled with -1e4, p_i = softmax_j s_ij, p_0 = 0, dropout on p, out_i = sum_j p_ij v_j
+ * The kernels leave the filled columns out: equal to the fill in float32 while max_{j<i} s_ij > -1e4 + 104.  Row 0 of out and its
+ * gradient contribution are exactly zero.  No [L x L] tensor is written; backward recomputes p from lse; no atomics (deterministic).
+ * delta [B, H, L] is scratch of the backward call: delta_i = sum_j p_ij dp_ij / sum_j p_ij, written by its row pass (dq) and read by
+ * its column pass (dk, dv) -- from the recomputed p, so that a one-column row cancels exactly and sum_j ds_ij vanishes
+ * (csrc/evae_attn.hip); `out` is the forward result.
+ * Supported: dh == 4, 1 <= L <= evae_causal_attn_max_len() (1536: the column pass keeps 40 L bytes of LDS within 64 KiB), any B * H
+ * < 2^31.  Anything else: EVAE_EINVAL, nothing launched.  evae_causal_attn_lds_bytes(L, pass): the LDS a workgroup of pass 0 (rows:
+ * forward, dq) or 1 (columns: dk, dv) takes, 0 when L is unsupported.
+ *
+ * Dropout (0 <= p_drop < 1; 0 draws nothing): Philox4x32-10, regenerated in the backward pass from (seed, offset).  Element e takes
+ * word e % 4 of quad e / 4, counter (quad_lo, quad_hi, offset_lo, offset_hi), key (seed_lo, seed_hi), keep <=> u01(word) >= p_drop,
+ * kept values times 1 / (1 - p_drop).  Attention: e = ((b H + h) L + i) L + j.  Element-wise: e = the flat index.
+ *
+ *   evae_elu_dropout_fwd   out = dropout(ELU(x))                 (utils/nn.py:298-299; p_drop = 0: the plain ELU of :293)
+ *   evae_elu_dropout_bwd   dx = dy * mask/(1-p) * ELU'(x)
+ *   evae_glu_res_fwd       out[m, c] = ab[m, c] * sigmoid(ab[m, C + c]) + x[m, c]     (GLU over channels + residual, :307-308;
+ *                          ab [M x 2C], x and out [M x C]: the pixels of a channels-last tensor)
+ *   evae_glu_res_bwd       dab from dout (the gradient into x is dout itself) */
+int evae_causal_attn_max_len(void);
+size_t evae_causal_attn_lds_bytes(int L, int pass);
+int evae_causal_attn_fwd(const float* q, const float* k, const float* v, int B, int H, int L, int dh, float p_drop, uint64_t seed,
+                         uint64_t offset, float* out, float* lse, evae_stream_t stream);
+int evae_causal_attn_bwd(const float* q, const float* k, const float* v, const float* out, const float* lse, const float* dout, int B,
+                         int H, int L, int dh, float p_drop, uint64_t seed, uint64_t offset, float* delta, float* dq, float* dk,
+                         float* dv, evae_stream_t stream);
+int evae_elu_dropout_fwd(const float* x, size_t n, float p_drop, uint64_t seed, uint64_t offset, float* out, evae_stream_t stream);
+int evae_elu_dropout_bwd(const float* dy, const float* x, size_t n, float p_drop, uint64_t seed, uint64_t offset, float* dx,
+                         evae_stream_t stream);
+int evae_glu_res_fwd(const float* ab, const float* x, int64_t M, int C, float* out, evae_stream_t stream);
+int evae_glu_res_bwd(const float* dout, const float* ab, int64_t M, int C, float* dab, evae_stream_t stream);
+
 /* Window convolutions over pre-split pixel images (csrc/evae_conv_win.h): the gated layers BETWEEN two layers of a convolutional
  * encoder stack (reference utils/nn.py:72-97, models/convHVAE_2level.py:21-46), whose activations then never exist as fp32
  * tensors.  A "pixel image" holds an activation [pixels x channels] (channels % 16 == 0) as three bf16 planes per 16 pixels x 16

@@ -995,7 +995,63 @@ def g26():
     save("g26_standard_epochs", **out)
 
 
+# ---- G27: the PixelSNAIL decoder of model_name 'pixelcnn' (utils/nn.py:148-562, models/PixelCNN.py) ----
+G27 = dict(seed=271, B=2, H=6, W=5)          # non-square on purpose
+
+
+def _g27_run(name, module, inputs):
+    """module: a freshly seeded reference module (float32 parameters).  One float32 forward first (CausalConv2d masks its weight_v in
+    place on a call: the stored parameters are the masked ones), then the float64 copy in eval mode: outputs, and the gradients of
+    sum(out * gout) wrt every input and parameter.  Stored: parameters and inputs float32, outputs and gradients float64."""
+    import copy
+    module.eval()
+    with torch.no_grad():
+        module(*[T(v) for v in inputs.values()])
+    out = {"p." + k: v.detach().numpy().copy() for k, v in module.state_dict().items()}
+    m64 = copy.deepcopy(module).double()
+    xs = {k: T(v).double().requires_grad_(True) for k, v in inputs.items()}
+    y = m64(*xs.values())
+    gout = np.random.RandomState(G27["seed"] + 1).randn(*y.shape).astype(np.float32)
+    (y * T(gout).double()).sum().backward()
+    for k, v in inputs.items():
+        out["x." + k] = v
+        out["dx." + k] = xs[k].grad.numpy()
+    out["gout"] = gout
+    out["out"] = y.detach().numpy()
+    for k, p_ in m64.named_parameters():
+        out["g." + k] = p_.grad.numpy()
+    save(name, **out)
+
+
+def g27():
+    """(a) CausalAttention(66, 130, 32), (b) GatedResBlock(16, 16, 3, conv='causal'), (c) PixelSNAIL([6, 5], 64, 64, 3, 1, 0, 64) on
+    [2, ., 6, 5] inputs, and (d) the names and shapes of the full pixelcnn model's state dict."""
+    import json
+    from utils.nn import CausalAttention, GatedResBlock, PixelSNAIL
+    from models.PixelCNN import VAE as PixelVAE
+    c = G27
+    rs = np.random.RandomState(c["seed"])
+    img = lambda ch: rs.randn(c["B"], ch, c["H"], c["W"]).astype(np.float32)
+    torch.manual_seed(c["seed"])
+    _g27_run("g27_attention", CausalAttention(66, 130, 32), {"query": img(66), "key": img(130)})
+    _g27_run("g27_gated_resblock", GatedResBlock(16, 16, 3, conv='causal'), {"input": img(16)})
+    _g27_run("g27_pixelsnail", PixelSNAIL([c["H"], c["W"]], 64, 64, 3, 1, 0, 64), {"input": img(3)})
+    model = PixelVAE(vae_args(model_name="pixelcnn"))
+    state = [[k, list(v.shape)] for k, v in model.state_dict().items()]
+    path = os.path.join(OUT, "g27_pixelcnn_state.json")
+    with open(path, "w") as f:
+        import inspect
+        import utils.nn as ref_nn
+        names = ("wn_linear", "WNConv2d", "shift_down", "shift_right", "CausalConv2d", "GatedResBlock", "causal_mask",
+                 "CausalAttention", "PixelBlock", "PixelSNAIL")
+        sig = lambda o: [[n, (None if p_.default is inspect.Parameter.empty else repr(p_.default))]
+                         for n, p_ in inspect.signature(getattr(o, "__wrapped__", o)).parameters.items()]
+        json.dump({"entries": state, "parameters": int(sum(p_.numel() for p_ in model.parameters())),
+                   "signatures": {n: sig(getattr(ref_nn, n)) for n in names}}, f, indent=0)
+    print("g27_pixelcnn_state.json: %d entries, %d parameters" % (len(state), sum(p_.numel() for p_ in model.parameters())))
+
+
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["g1_g2", "g3", "g4", "g5", "g6", "g6_conv", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16", "g17", "g18", "g19", "g20", "g21", "g22", "g23", "g24", "g25", "g26"]
+    which = sys.argv[1:] or ["g1_g2", "g3", "g4", "g5", "g6", "g6_conv", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16", "g17", "g18", "g19", "g20", "g21", "g22", "g23", "g24", "g25", "g26", "g27"]
     for w in which:
         globals()[w]()
