@@ -19,11 +19,13 @@ LOG_2_PI = math.log(2 * math.pi)
 
 
 # ---- dropout masks ---------------------------------------------------------------------------------------------------
-def flat_keep_mask(n, p_drop, seed, offset):
-    """keep [n] (bool): element e takes word e % 4 of quad e // 4, counter (quad_lo, quad_hi, offset_lo, offset_hi), key
-    (seed_lo, seed_hi); keep <=> u01(word) >= p_drop (compared in float32)"""
-    n = int(n)
-    quad = np.arange((n + 3) // 4, dtype=np.uint64)
+def flat_keep_mask(n, p_drop, seed, offset, first=0):
+    """keep [n] (bool) of the elements first, first + 1, ..., first + n - 1 (first: a multiple of 4, < 2^64): element e takes word
+    e % 4 of quad e // 4, counter (quad_lo, quad_hi, offset_lo, offset_hi), key (seed_lo, seed_hi); keep <=> u01(word) >= p_drop
+    (compared in float32)"""
+    n, first = int(n), int(first)
+    assert first >= 0 and first % 4 == 0 and first + n <= 1 << 64, (first, n)
+    quad = np.uint64(first // 4) + np.arange((n + 3) // 4, dtype=np.uint64)
     offset = int(offset)
     ctr = (quad & pr.MASK, quad >> np.uint64(32), np.uint64(offset & 0xFFFFFFFF), np.uint64((offset >> 32) & 0xFFFFFFFF))
     words = np.stack(pr.philox4x32_10(ctr, pr.seed_key(seed)), axis=1).reshape(-1)[:n]
@@ -33,6 +35,25 @@ def flat_keep_mask(n, p_drop, seed, offset):
 def attn_keep_mask(BH, L, p_drop, seed, offset):
     """keep [BH, L, L]: element e = ((b H + h) L + i) L + j of the flattened probabilities"""
     return flat_keep_mask(BH * L * L, p_drop, seed, offset).reshape(BH, L, L)
+
+
+def attn_keep_mask_head(bh, L, p_drop, seed, offset, wrap_bits=None):
+    """keep [L, L] of head bh = b H + h alone: attn_keep_mask(...)[bh] without the heads before it.  wrap_bits: the mask a kernel
+    would draw that kept only the low `wrap_bits` bits of the element index (a multiple-of-4 boundary: wrap_bits >= 2) -- what a
+    test shows its case to differ from, never a reference value."""
+    n = L * L
+    e0 = int(bh) * n
+    lead = e0 % 4                                       # (odd L: the head starts inside a quad)
+    if wrap_bits is None:
+        return flat_keep_mask(lead + n, p_drop, seed, offset, e0 - lead)[lead:].reshape(L, L)
+    period = 1 << wrap_bits
+    parts, e = [], e0
+    while e < e0 + n:                                   # runs of elements between two multiples of the period
+        run = min(e0 + n, (e // period + 1) * period) - e
+        skip = (e % period) % 4
+        parts.append(flat_keep_mask(skip + run, p_drop, seed, offset, e % period - skip)[skip:])
+        e += run
+    return np.concatenate(parts).reshape(L, L)
 
 
 # ---- pieces ----------------------------------------------------------------------------------------------------------------
@@ -186,16 +207,23 @@ def pixelcnn_decoder_mean(sd, x_img, z1, z2):
     return torch.sigmoid(F.conv2d(top, sd["p_x_mean.conv.weight"], sd["p_x_mean.conv.bias"])).reshape(B, -1)
 
 
-def pixelcnn_loss(sd, x, eps2, eps1, exemplars, beta=1.0, input_size=(1, 28, 28)):
-    """(loss, RE, KL) per row of the eval-mode `pixelcnn` model with the exemplar prior over the encodings of `exemplars` [C, D]
-    (no leave-one-out mask: evaluation), binary inputs.  eps2 / eps1: the noise of z2 and of z1."""
-    B = x.shape[0]
-    img = x.view(B, *input_size)
+def pixelcnn_posterior(sd, img, eps2, eps1):
+    """(z1, q1_mu, q1_lv, z2, q2_mu, q2_lv): the samples of q(z2 | x) and q(z1 | x, z2) for images [B, 1, 28, 28] and their noise"""
+    B = img.shape[0]
     q2_mu, q2_lv = _heads(sd, "q_z", _gated_conv_stack(sd, "q_z_layers", img, _ENC_WIDE).reshape(B, -1))
     z2 = q2_mu + eps2 * torch.exp(0.5 * q2_lv)
     joint = torch.cat((_gated_conv_stack(sd, "q_z1_layers_x", img, _ENC_NARROW).reshape(B, -1), _gated_dense(sd, "q_z1_layers_z2.0", z2)), 1)
     q1_mu, q1_lv = _heads(sd, "q_z1", _gated_dense(sd, "q_z1_layers_joint.0", joint))
     z1 = q1_mu + eps1 * torch.exp(0.5 * q1_lv)
+    return z1, q1_mu, q1_lv, z2, q2_mu, q2_lv
+
+
+def pixelcnn_loss(sd, x, eps2, eps1, exemplars, beta=1.0, input_size=(1, 28, 28)):
+    """(loss, RE, KL) per row of the eval-mode `pixelcnn` model with the exemplar prior over the encodings of `exemplars` [C, D]
+    (no leave-one-out mask: evaluation), binary inputs.  eps2 / eps1: the noise of z2 and of z1."""
+    B = x.shape[0]
+    img = x.view(B, *input_size)
+    z1, q1_mu, q1_lv, z2, q2_mu, q2_lv = pixelcnn_posterior(sd, img, eps2, eps1)
     p1_mu, p1_lv = _heads(sd, "p_z1", _gated_dense(sd, "p_z1_layers_z2.1", _gated_dense(sd, "p_z1_layers_z2.0", z2)))
     mean = pixelcnn_decoder_mean(sd, img, z1, z2)
     probs = mean.clamp(1e-5, 1.0 - 1e-5)

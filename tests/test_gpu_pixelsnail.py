@@ -4,8 +4,10 @@ reference goldens G27.
 
 Tolerance of every compared tensor: the yardstick is the error of the SAME restatement evaluated in float32 on the CPU against its
 float64 value, on the same inputs, as max |a - b| over the tensor; the HIP result gets 4 x that, plus one float32 ulp of the
-tensor's largest magnitude (the kernels sum up to 783 terms in another order, and large GEMMs run split-bf16 at fp32-GEMM accuracy).
+tensor's largest magnitude (the kernels sum up to 1535 terms in another order, and large GEMMs run split-bf16 at fp32-GEMM accuracy).
 Each figure is printed before it is asserted (ratio = HIP error / yardstick)."""
+import math
+
 import numpy as np
 import pytest
 import torch
@@ -16,7 +18,11 @@ import smoke_case
 
 pytestmark = pytest.mark.gpu
 
-ATTN_SHAPES = [(2, 8, 784), (3, 1, 1), (1, 3, 2), (5, 1, 65), (1, 1, 257)]           # (B, H, L): B*H = 16, 3, 3, 5, 1
+ATTN_MAX_LEN = 1536                                                                  # ops.causal_attn_max_len(): asserted below
+ATTN_SHAPES = [(2, 8, 784), (3, 1, 1), (1, 3, 2), (5, 1, 65), (1, 1, 257),           # (B, H, L): B*H = 16, 3, 3, 5, 1
+               # a thread takes pair p, p + 256, ...: exactly 256 pairs, 257 (odd L: its middle row once), and three full rounds
+               # at the LDS limit, 1535 with the middle row in the last one
+               (1, 1, 512), (1, 2, 513), (1, 1, ATTN_MAX_LEN - 1), (1, 2, ATTN_MAX_LEN)]
 P_DROP, RNG = 0.1, (0x1234567887654321, 0x100000003)                                 # (seed, offset): both halves of each in use
 
 
@@ -122,15 +128,68 @@ def test_attention_dropout_counter_advances(ops):
     assert torch.equal(a, again)
 
 
+def _head_rows(t, B, H, L, bh):
+    """head bh = b H + h of a device tensor of rows [B*L, H*4] -> host [1, L, 4]"""
+    b, h = divmod(bh, H)
+    return host(t.view(B, L, H, 4)[b, :, h]).reshape(1, L, 4).copy()
+
+
+def test_attention_dropout_element_index_is_64_bit(ops):
+    """B H L^2 = 1.72e10 probabilities: head 1820 holds element e = 2^32 (in row 682), head 7281 holds e = 2^34, from where on the
+    quad's second counter word is 1.  Four heads against the restatement under the mask of THEIR element indices; the two straddling
+    heads' masks differ from what an index cut to 32 bits (a quad cut to 32 bits) would draw, so this case tells the two apart."""
+    B, H, L = 1821, 4, ATTN_MAX_LEN
+    n = L * L
+    straddle = {1820: 32, 7281: 34}                                     # head: log2 of the element index it crosses
+    for bh, bits in straddle.items():
+        assert bh * n < 1 << bits < (bh + 1) * n
+    assert ((1 << 32) - 1820 * n) // L == 682 and B * H * n > 1 << 34
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(2790)
+    q, k, v, go = (torch.randn(B * L, H * 4, generator=gen, device="cuda") for _ in range(4))
+    for a in (q, k, v):
+        a.requires_grad_(True)
+    out = ops.causal_attn(q, k, v, B, L, H, P_DROP, rng=RNG)
+    out.backward(go)
+    lower = np.tril(np.ones((L, L), bool), -1)                          # the entries j < i: the ones the kernel draws
+    res = []
+    for bh in (0, 1820, 7281, 7283):
+        qh, kh, vh, goh = (_head_rows(a, B, H, L, bh) for a in (q, k, v, go))
+        assert np.abs(qh[0] @ kh[0].T).max() / 2 < 50
+        keep = psr.attn_keep_mask_head(bh, L, P_DROP, *RNG)
+        assert 0 < keep.mean() < 1
+        if bh in straddle:
+            bits = straddle[bh]
+            wrapped = psr.attn_keep_mask_head(bh, L, P_DROP, *RNG, wrap_bits=bits)
+            row = ((1 << bits) - bh * n) // L                           # the row that holds the crossing
+            differ = int(((wrapped != keep) & lower).sum())
+            print("head %d: a %d-bit index draws %d other entries with j < i, all in rows >= %d" % (bh, bits, differ, row))
+            assert np.array_equal(wrapped[:row], keep[:row]) and differ > 0
+
+        def ref(dtype):
+            t = [torch.from_numpy(a).to(dtype).requires_grad_(True) for a in (qh, kh, vh)]
+            o = psr.causal_attention_core(*t, keep[None], P_DROP)
+            (o * torch.from_numpy(goh).to(dtype)).sum().backward()
+            return [o.detach().numpy()] + [a.grad.numpy() for a in t]
+
+        got = [_head_rows(a, B, H, L, bh) for a in (out, q.grad, k.grad, v.grad)]
+        res += [close("attn B%d H%d L%d head %d %s" % (B, H, L, bh, name), g, a, b)
+                for name, g, a, b in zip(("out", "dq", "dk", "dv"), got, ref(torch.float64), ref(torch.float32))]
+    assert_all(res)
+
+
 def test_attention_refuses_unsupported_shapes(ops):
     from evae._lib import EvaeError
     x8 = torch.zeros(2 * 16, 2 * 8, device="cuda")
     with pytest.raises(EvaeError, match="head width"):
         ops.causal_attn(x8, x8, x8, 2, 16, 2)                            # dh = 8
-    too_long = ops.causal_attn_max_len() + 1
-    xl = torch.zeros(too_long, 4, device="cuda")
+    longest = ops.causal_attn_max_len()
+    assert longest == ATTN_MAX_LEN
+    xl = torch.zeros(longest + 1, 4, device="cuda")
     with pytest.raises(EvaeError, match="LDS"):
-        ops.causal_attn(xl, xl, xl, 1, too_long, 1)
+        ops.causal_attn(xl, xl, xl, 1, longest + 1, 1)
+    ok = ops.causal_attn(xl[:longest], xl[:longest], xl[:longest], 1, longest, 1)        # the longest itself is accepted
+    assert ok.shape == (longest, 4) and float(ok.abs().max()) == 0.0
 
 
 # ---- element-wise operators --------------------------------------------------------------------------------------------
@@ -343,12 +402,172 @@ def test_model_decoder_is_causal(model_case):
     assert torch.equal(m1[:, :401], m2[:, :401]) and not torch.equal(m1[:, 401:], m2[:, 401:])
 
 
-def test_model_generates(model_case):
-    model = model_case["model"]
-    torch.manual_seed(276)
-    z = torch.randn(B_MODEL, 40, device="cuda")
-    out = model.generate_x_from_z(z)
-    assert out.shape == (B_MODEL, 784) and bool(((out > 0) & (out < 1)).all())
+def _decoder_mean_ref(sd, dtype, x, z1, z2):
+    """psr.pixelcnn_decoder_mean on whole 28-row images x [B, 784] -> [B, 784] (numpy)"""
+    s = {k: v.to(dtype).clone() for k, v in sd.items()}
+    with torch.no_grad():
+        return psr.pixelcnn_decoder_mean(s, torch.from_numpy(x).to(dtype).view(-1, 1, 28, 28), torch.from_numpy(z1).to(dtype),
+                                         torch.from_numpy(z2).to(dtype)).numpy()
+
+
+@pytest.fixture(scope="module")
+def decoder_case(model_case):
+    """fixed z1, z2 and a binary x for the decoder alone; the restatement's means on the WHOLE image in float64 and float32"""
+    rs = np.random.RandomState(281)
+    z1, z2 = rs.randn(B_MODEL, 40).astype(np.float32), rs.randn(B_MODEL, 40).astype(np.float32)
+    x = gi.binary_images(282, B_MODEL)
+    mean64, mean32 = (_decoder_mean_ref(model_case["sd"], dt, x, z1, z2) for dt in (torch.float64, torch.float32))
+    return dict(z1=z1, z2=z2, x=x, mean64=mean64, mean32=mean32)
+
+
+# B = 1 with one and two rows: 28 and 56 pixel rows, less than any GEMM tile
+@pytest.mark.parametrize("B,r", [(2, 1), (2, 2), (2, 3), (2, 14), (2, 27), (2, 28), (1, 1), (1, 2)])
+def test_truncated_decoder_matches_full_height_ref(model_case, decoder_case, B, r):
+    """the pass pixelcnn_generate runs for a pixel of row r - 1 -- the decoder on the first r rows -- against rows < r of the
+    restatement on all 28 rows (not bit-equal to a full pass of the kernels: another geometry may sum in another order)"""
+    model, d = model_case["model"], decoder_case
+    x = dev(d["x"][:B]).view(B, 1, 28, 28)
+    with torch.no_grad():
+        latent = model._decoder_images(dev(d["z1"][:B]), dev(d["z2"][:B]))
+        got = model.p_x_mean(model.pixelcnn(torch.cat((x[:, :, :r], latent[:, :, :r]), 1)))
+    assert got.shape == (B, 1, r, 28)
+    rows = lambda m: m.reshape(B_MODEL, 1, 28, 28)[:B, :, :r]
+    assert_all([close("decoder on %d of 28 rows, B = %d" % (r, B), host(got), rows(d["mean64"]), rows(d["mean32"]))])
+
+
+GENERATION_SEED = 284
+
+
+def test_generation_is_consistent_with_its_draws(model_case, monkeypatch):
+    """pixelcnn_generate with torch.bernoulli replaced by thresholds against a fixed table u [B, 784]: the probability it thresholds
+    at call t and the means it returns are the restatement's, teacher-forced in ONE full-height pass on the pixels it drew -- so
+    every truncated pass saw exactly the draws before it, in raster order -- and every drawn pixel is (u < mean)."""
+    model, D = model_case["model"], 784
+    rs = np.random.RandomState(283)
+    z1, z2 = rs.randn(B_MODEL, 40).astype(np.float32), rs.randn(B_MODEL, 40).astype(np.float32)
+    u = np.random.RandomState(GENERATION_SEED).rand(B_MODEL, D).astype(np.float32)
+    u_dev = dev(u)
+    probs, draws, calls = [], [], [0]
+
+    def threshold(p, *args, **kwargs):
+        t = calls[0]
+        calls[0] += 1
+        if t >= D or args or kwargs or p.numel() != B_MODEL:
+            probs.append(None)
+            return torch.zeros_like(p)
+        probs.append(p.detach().clone().reshape(B_MODEL))
+        draws.append((u_dev[:, t].view_as(p) < p).float())
+        return draws[-1].clone()
+
+    monkeypatch.setattr(torch, "bernoulli", threshold)
+    out = model.pixelcnn_generate(dev(z1), dev(z2))
+    monkeypatch.undo()
+    assert calls[0] == D and all(p is not None for p in probs)           # one draw per pixel, each from B probabilities
+    assert out.shape == (B_MODEL, D) and bool(((out > 0) & (out < 1)).all())
+    x_drawn = host(torch.stack([d.reshape(B_MODEL) for d in draws], dim=1))
+    p_used = host(torch.stack(probs, dim=1))
+    assert set(np.unique(x_drawn)) <= {0.0, 1.0} and 0 < x_drawn.mean() < 1
+    mean64, mean32 = (_decoder_mean_ref(model_case["sd"], dt, x_drawn, z1, z2) for dt in (torch.float64, torch.float32))
+    res = [close("generate: means returned", host(out), mean64, mean32),
+           close("generate: probability thresholded at each of the 784 calls", p_used, mean64, mean32)]
+    assert_all(res)
+    _, err, yard, ulp = res[1][1]
+    bar, gap = 4.0 * yard + ulp, np.abs(u.astype(np.float64) - mean64).min()
+    print("generate: smallest |u - mean64| %.3e = %.1f x the bar %.3e" % (gap, gap / bar, bar))
+    assert gap > 8.0 * bar                                               # (input condition: no threshold within reach of the error)
+    assert np.array_equal(x_drawn, (u.astype(np.float64) < mean64).astype(np.float32))
+
+
+def test_reconstruct_x_generates_from_the_posterior_sample(model_case):
+    """reconstruct_x hands pixelcnn_generate the z1 and z2 that forward() sampled for the injected noise, and returns its result"""
+    c = model_case
+    model = c["model"]
+    draws = iter([dev(e) for e in c["eps"]])
+    seen = []
+    model._draw_eps = lambda like: next(draws)
+    model.pixelcnn_generate = lambda z1, z2: seen.append((z1, z2)) or "generated"
+    try:
+        with torch.no_grad():
+            got = model.reconstruct_x(dev(c["x"]))
+    finally:
+        del model._draw_eps, model.pixelcnn_generate
+    assert got == "generated" and len(seen) == 1 and next(draws, None) is None
+
+    def ref(dtype):
+        s = {k: v.to(dtype).clone() for k, v in c["sd"].items()}
+        eps2, eps1 = (torch.from_numpy(e).to(dtype) for e in c["eps"])
+        with torch.no_grad():
+            lat = psr.pixelcnn_posterior(s, torch.from_numpy(c["x"]).to(dtype).view(-1, 1, 28, 28), eps2, eps1)
+        return lat[0].numpy(), lat[3].numpy()
+
+    (z1_64, z2_64), (z1_32, z2_32) = ref(torch.float64), ref(torch.float32)
+    assert_all([close("reconstruct_x: z1", host(seen[0][0]), z1_64, z1_32), close("reconstruct_x: z2", host(seen[0][1]), z2_64, z2_32)])
+
+
+# ---- the IWAE estimate: calls of IWAE_CHUNK_ROWS rows ----------------------------------------------------------------------
+def test_iwae_chunks_match_ref(model_case, monkeypatch):
+    """two images x S = 3 in calls of 4 rows (a full chunk and a ragged one of 2) and in one call: the per-row losses and the
+    estimate against the restatement on all six rows, the noise served row by row from two fixed tables"""
+    import models.PixelCNN as pixelcnn_module
+    from utils.evaluation import calculate_likelihood
+    c = model_case
+    model, args, S = c["model"], c["args"], 3
+    assert type(model).__module__ == pixelcnn_module.__name__ and pixelcnn_module.IWAE_CHUNK_ROWS == 100
+    n_rows = B_MODEL * S
+    rs = np.random.RandomState(285)
+    tables = [rs.randn(n_rows, 40).astype(np.float32) for _ in range(2)]            # eps2, eps1
+    tables_dev = [dev(t) for t in tables]
+    xs = np.repeat(c["x"], S, axis=0)
+
+    def ref(dtype):
+        s = {k: v.to(dtype).clone() for k, v in c["sd"].items()}
+        with torch.no_grad():
+            loss = psr.pixelcnn_loss(s, *(torch.from_numpy(a).to(dtype) for a in (xs, tables[0], tables[1], c["ex"])))[0]
+            est = -(torch.logsumexp(-loss.view(B_MODEL, S), 1) - math.log(S)).mean()
+        return loss.numpy(), np.array([est.item()], dtype=loss.numpy().dtype)
+
+    (rows64, est64), (rows32, est32) = ref(torch.float64), ref(torch.float32)
+
+    def served():
+        """a noise hook over the two tables: every calculate_loss call draws z2's noise, then z1's, for its own rows"""
+        cursor, n_calls = [0, 0], [0]
+
+        def draw(like):
+            which = n_calls[0] % 2
+            n_calls[0] += 1
+            lo, hi = cursor[which], cursor[which] + like.shape[0]
+            assert hi <= n_rows and tuple(like.shape[1:]) == (40,), (which, lo, like.shape)
+            cursor[which] = hi
+            return tables_dev[which][lo:hi]
+        return draw, cursor
+
+    def run(fn):
+        draw, cursor = served()
+        model._draw_eps = draw
+        try:
+            with torch.no_grad():
+                out = fn()
+        finally:
+            del model._draw_eps
+        assert cursor == [n_rows, n_rows]                                # both tables consumed, exactly once
+        return out
+
+    with torch.no_grad():
+        centres, logvar = model.q_z(dev(c["ex"]), prior=True)
+    emb = (centres, logvar, torch.arange(C_MODEL, device="cuda"))
+    x = dev(c["x"])
+    loader = torch.utils.data.DataLoader(torch.utils.data.TensorDataset(torch.from_numpy(c["x"]), torch.arange(B_MODEL)), batch_size=B_MODEL)
+    whole = host(run(lambda: model.importance_sample_losses(x, S, emb)))
+    monkeypatch.setattr(pixelcnn_module, "IWAE_CHUNK_ROWS", 4)
+    chunked = host(run(lambda: model.importance_sample_losses(x, S, emb)))
+    estimate = run(lambda: calculate_likelihood(args, model, loader, S=S, exemplars_embedding=emb))
+    res = [close("IWAE rows, calls of 4 + 2", chunked, rows64, rows32), close("IWAE rows, one call", whole, rows64, rows32),
+           close("IWAE estimate, calls of 4 + 2", np.array([estimate]), est64, est32)]
+    _, _, yard, ulp = res[0][1]
+    apart = np.abs(chunked.astype(np.float64) - whole).max()
+    print("IWAE rows, chunked against one call: %.3e apart, bar %.3e" % (apart, 4.0 * yard + ulp))
+    assert_all(res)
+    assert apart <= 4.0 * yard + ulp
 
 
 def test_model_evaluation_entry_points_run(model_case):

@@ -149,6 +149,39 @@ def test_dropout_mask_keeps_its_share():
     assert psr.flat_keep_mask(64, 0.0, 1, 1).all()
 
 
+def test_per_head_masks_are_slices_of_the_whole_mask():
+    """an even L (every head starts on a quad) and an odd one (heads start inside a quad); a wrap no index reaches changes nothing,
+    one inside the tensor restarts the stream there"""
+    for BH, L in ((5, 6), (4, 5)):
+        whole = psr.attn_keep_mask(BH, L, 0.3, 1234, 7)
+        assert 0 < whole.mean() < 1
+        for bh in range(BH):
+            assert np.array_equal(psr.attn_keep_mask_head(bh, L, 0.3, 1234, 7), whole[bh]), (L, bh)
+            assert np.array_equal(psr.attn_keep_mask_head(bh, L, 0.3, 1234, 7, wrap_bits=8), whole[bh]), (L, bh)
+    flat = psr.flat_keep_mask(5 * 36, 0.3, 1234, 7)
+    wrapped = np.concatenate([psr.attn_keep_mask_head(bh, 6, 0.3, 1234, 7, wrap_bits=6).reshape(-1) for bh in range(5)])
+    assert np.array_equal(wrapped, np.concatenate([flat[:64], flat[:64], flat[:52]])) and not np.array_equal(wrapped, flat)
+    assert np.array_equal(psr.flat_keep_mask(21, 0.3, 1234, 7, first=40), flat[40:61])
+    with pytest.raises(AssertionError):
+        psr.flat_keep_mask(8, 0.3, 1234, 7, first=2)
+
+
+def test_mask_offset_reaches_the_second_counter_word():
+    """first = 2^34 - 8: quads 2^32 - 2, 2^32 - 1, 2^32 -- counter words (0xFFFFFFFE, 0), (0xFFFFFFFF, 0) and (0, 1)"""
+    import philox_ref as pr
+    seed, offset, p = 0x1234567887654321, 0x100000003, 0.3
+    got = psr.flat_keep_mask(12, p, seed, offset, first=(1 << 34) - 8)
+    off = (offset & 0xFFFFFFFF, offset >> 32)
+    want = []
+    for lo, hi in ((0xFFFFFFFE, 0), (0xFFFFFFFF, 0), (0, 1)):
+        words = pr.philox4x32_10((np.uint64(lo), np.uint64(hi), np.uint64(off[0]), np.uint64(off[1])), pr.seed_key(seed))
+        want += [bool(pr.u01(w) >= np.float32(p)) for w in words]
+    assert got.tolist() == want and 0 < sum(want) < 12
+    # ... and is not what the low counter word alone gives: quad 2^32 is not quad 0
+    assert np.array_equal(psr.flat_keep_mask(12, p, seed, offset), psr.flat_keep_mask(12, p, seed, offset, first=0))
+    assert not np.array_equal(psr.flat_keep_mask(256, p, seed, offset, first=1 << 34), psr.flat_keep_mask(256, p, seed, offset))
+
+
 def test_attention_abi_refuses_unsupported_shapes_without_launching():
     from evae import _lib
     lib = _lib.load()
