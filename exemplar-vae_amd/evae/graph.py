@@ -236,7 +236,7 @@ class GraphedTrainStep:
         wh, wg = named.get("q_z_layers.0.h.weight"), named.get("q_z_layers.0.g.weight")
         if wh is None or wg is None or not (wh.is_contiguous() and wg.is_contiguous() and wh.dtype == torch.float32):
             return None
-        lib = fused_vae._lib.load()
+        lib = _lib.load()
         H, D = wh.shape
         prep = ops._workspace("u8prep", lib.evae_dense_u8_prepared_bytes(H, D), wh.device)
         h.prep = (prep.data_ptr(), wh.data_ptr(), wg.data_ptr())

@@ -1,0 +1,150 @@
+"""The raw-launch layer of the fused training steps (evae/fused_vae.py, evae/fused_std.py): the one pointer conversion, the
+launcher over the dense entry points of the C ABI, the two job-table fillers, the beta pair.  No autograd, caller-owned outputs.
+
+The steps built on it are stage functions over one per-step state object.  Every change to them keeps four invariants; they are
+held by tests/test_gpu_step_trace.py (what a step issues, record for record, against a recorded golden), not by a reader's eye:
+
+* ISSUE ORDER IS BEHAVIOUR.  The order launches, event records and stream waits are issued in is the order the captured hipGraph
+  starts them in: the leaves of fused_vae's backward pass issued elsewhere replayed at 0.82-1.2 ms against 0.66.  Stages are
+  called in that order; a stage that is interleaved with another stays interleaved.
+* THE STREAM CURRENT AT EACH ALLOCATION IS BEHAVIOUR.  The caching allocator pools per stream: an allocation-order change once
+  handed a live scratch buffer of the prior's launch to the other stream.  Every torch.empty keeps its place relative to the
+  `with torch.cuda.stream(side)` blocks and to its neighbours.
+* LIFETIMES DO NOT GET SHORTER.  Launches on the other stream read buffers through raw pointers, with no record_stream.  A stage
+  keeps no tensor of its own: what it allocates goes on the step state -- a pass's temporaries on st.fwd / st.bwd, cleared where
+  that pass returns; what the backward pass needs on the state itself, dropped where the backward pass returns.
+* MODULE-LEVEL SWITCHES KEEP THEIR NAMES AND THEIR READ TIME: import-time constants stay import-time, per-call reads
+  (node_merge(), the os.environ reads inside the passes) stay per-call.  evae/graph.py and tools/ read them by name."""
+import ctypes as C
+import os
+
+import torch
+
+from . import _lib
+
+
+def vp(v):
+    """tensor | int address | None -> c_void_p | None: the single pointer conversion"""
+    if v is None:
+        return None
+    return C.c_void_p(v if isinstance(v, int) else v.data_ptr())
+
+
+from . import ops       # noqa: E402  (evae.ops takes vp from here: it has to exist before ops is imported)
+
+
+def beta_args(beta):
+    """(beta_dev, beta_host) as the kernels take them: the device scalar and 0.0, or None and the float"""
+    if torch.is_tensor(beta):
+        return beta, 0.0
+    return None, float(beta)
+
+
+def ptr(t):
+    return t if isinstance(t, int) else t.data_ptr()
+
+
+def wgrad_jobs(jobs):
+    """(dy, M, N, ldy, x, K, ldx, dw, db) per job -> (evae_wgrad_job_t array as c_void_p, count, the array: keep it until the
+    launch is issued).  Which jobs share a launch is the caller's rule."""
+    arr = (_lib.WgradJob * len(jobs))()
+    for a, (dy, M, N, ldy, x, K, ldx, dw, db) in zip(arr, jobs):
+        a.dy, a.x, a.dw, a.db = ptr(dy), ptr(x), ptr(dw), ptr(db)
+        a.M, a.N, a.K, a.ldy, a.ldx = M, N, K, ldy, ldx
+    return C.cast(arr, C.c_void_p), len(jobs), arr
+
+
+def wgrad_finish_jobs(jobs):
+    """(byte_rows, M, N, K, ldy, ldx, x_scale, dw, db, workspace) per job -> the same for evae_wgrad_finish_job_t"""
+    arr = (_lib.WgradFinishJob * len(jobs))()
+    for a, (byte_rows, M, N, K, ldy, ldx, x_scale, dw, db, ws) in zip(arr, jobs):
+        a.byte_rows, a.M, a.N, a.K, a.ldy, a.ldx = byte_rows, M, N, K, ldy, ldx
+        a.x_scale, a.dw, a.db, a.ws, a.ws_bytes = x_scale, ptr(dw), ptr(db), ws.data_ptr(), ws.numel()
+    return C.cast(arr, C.c_void_p), len(jobs), arr
+
+
+class Launcher:
+    """Thin raw launchers over the C ABI (no autograd, caller-owned outputs)."""
+
+    def __init__(self, device, stream=None, prefix="", suffix="", pipes=True):
+        """Launches go to `stream` (default: the current one) and take their split-K workspaces from buffers named
+        prefix + name + suffix, so that two launchers never share scratch memory.  The names are behaviour: a captured graph has
+        the addresses baked in and ops._workspace keys on the name.  pipes=False: no evae_gemm_x6_applies query per launch for
+        the roofline probe's pipe label -- for steps whose launches the probe never records."""
+        self.lib = _lib.load()
+        self.dev = device
+        self.st = ops._stream() if stream is None else C.c_void_p(stream.cuda_stream)
+        self.pfx, self.sfx, self.pipes = prefix, suffix, pipes
+
+    def ws(self, name, nbytes):
+        return ops._workspace(self.pfx + name + self.sfx, nbytes, self.dev)
+
+    _side = {}
+
+    def side_stream(self, one_stream=False):
+        """Second stream for the decoder chain of the batch rows: it only meets the exemplar-prior chain at the ELBO (forward)
+        and at dz (backward), so the two chains of small launches run side by side, captured as parallel branches of the
+        step's hipGraph.  Collectives of the sharded prior stay on the main stream.  one_stream: the caller's own stream."""
+        if one_stream:
+            return torch.cuda.current_stream(self.dev)
+        key = self.dev.index if self.dev.index is not None else torch.cuda.current_device()
+        st = Launcher._side.get(key)
+        if st is None:
+            st = Launcher._side[key] = torch.cuda.Stream(device=self.dev, priority=int(os.environ.get("EVAE_SIDE_PRIORITY", "-1")))
+        return st
+
+    def _pipe(self, M, N, gated, flops, fits=True):
+        return ops.gemm_pipe(M, N, gated, flops) if (fits and self.pipes) else (None, "fp32-mfma")
+
+    def gated_fwd(self, x, rows, M, K, ldx, wh, bh, wg, bg, N, out, h, s):
+        nb = self.lib.evae_dense_fwd_workspace_bytes(M, K, N, 1)
+        w = self.ws("fwd", nb)
+        ex_, pipe_ = self._pipe(M, N, True, 2.0 * M * K * 2 * N, rows is None)
+        ops.probed("gated_dense_fwd M=%d K=%d N=%d%s" % (M, K, N, " (row gather)" if rows is not None else ""), 2.0 * M * K * 2 * N,
+                   lambda: _lib.check(self.lib.evae_gated_dense_fwd(vp(x), vp(rows), M, K, ldx, vp(wh), vp(bh), vp(wg), vp(bg),
+                                                                    N, vp(out), vp(h), vp(s), vp(w), w.numel(), self.st),
+                                      "gated_fwd"), executed=ex_, pipe=pipe_)
+
+    def linear_fwd(self, x, M, K, ldx, w_, b, N, act, lo, hi, y, pre):
+        nb = self.lib.evae_dense_fwd_workspace_bytes(M, K, N, 0)
+        w = self.ws("fwd", nb)
+        _lib.check(self.lib.evae_linear_fwd(vp(x), None, M, K, ldx, vp(w_), vp(b), N, act, lo, hi, vp(y), vp(pre),
+                                            vp(w), w.numel(), self.st), "linear_fwd")
+
+    def bwd_data(self, dy1, w1, dy2, w2, M, N, ldy, K, out_prev, s_prev, out, dg, ldo, wT=None):
+        """wT: the transposed weights prepared by the step's head launch, or None (then evae_dense_bwd_data_wt IS
+        evae_dense_bwd_data: both are dense_bwd_data_core, csrc/evae_dense.hip)"""
+        nb = self.lib.evae_dense_bwd_data_workspace_bytes(M, N, K, 2 if dy2 is not None else 1)
+        w = self.ws("dgrad", nb)
+        fl_ = 2.0 * M * N * K * (2 if dy2 is not None else 1)
+        ex_, pipe_ = self._pipe(M, K, False, fl_, N % 4 == 0 and ldy % 4 == 0)
+        ops.probed("dense_bwd_data M=%d N=%d%s K=%d%s" % (M, N, "+%d" % N if dy2 is not None else "", K,
+                                                          " (gate-backward epilogue)" if out_prev is not None else ""), fl_,
+                   lambda: _lib.check(self.lib.evae_dense_bwd_data_wt(vp(dy1), vp(w1), vp(dy2), vp(w2), M, N, ldy, K, vp(out_prev),
+                                                                      vp(s_prev), vp(out), vp(dg), ldo, vp(wT), vp(w), w.numel(),
+                                                                      self.st), "bwd_data"), executed=ex_, pipe=pipe_)
+
+    def bwd_weight(self, dy, M, N, ldy, x, rows, K, ldx, dw, db, phase=0, ws_name="wgrad", finish_on=None):
+        """phase 1 / 2: the split-K GEMM and its finish as separate calls (finish_on = the launcher whose stream runs it)"""
+        nb = self.lib.evae_dense_bwd_weight_workspace_bytes(M, N, K)
+        w = self.ws(ws_name, nb)
+        if phase == 0:
+            # (a narrow output over many rows -- the heads' [40 x 300] over all C + B rows -- streams its operands once: an HBM entry)
+            ops.probed("dense_bwd_weight M=%d N=%d K=%d (+db, split-K GEMM + finish)" % (M, N, K), 2.0 * M * N * K,
+                       hbm_bytes=(4.0 * M * (N + K)) if (N <= 64 and M >= 2048 and rows is None) else None, fn=
+                       lambda: _lib.check(self.lib.evae_dense_bwd_weight(vp(dy), M, N, ldy, vp(x), vp(rows), K, ldx, vp(dw),
+                                                                         vp(db), 0, vp(w), w.numel(), self.st), "bwd_weight"))
+        else:
+            st = self.st if finish_on is None else finish_on.st
+            call = lambda: _lib.check(self.lib.evae_dense_bwd_weight_phased(vp(dy), M, N, ldy, vp(x), vp(rows), K, ldx, vp(dw),
+                                                                            vp(db), 0, vp(w), w.numel(), phase, st), "bwd_weight_phased")
+            if phase == 1:
+                ops.probed("dense_bwd_weight M=%d N=%d K=%d (+db, split-K GEMM; its planes are summed by the step's last grouped launch)"
+                           % (M, N, K), 2.0 * M * N * K, call)
+            else:
+                call()
+
+    def bwd_weight_group(self, jobs):
+        """ONE launch for up to six thin weight gradients (evae_dense_bwd_weight_group)"""
+        arr, n, _keep = wgrad_jobs(jobs)
+        _lib.check(self.lib.evae_dense_bwd_weight_group(arr, n, self.st), "bwd_weight_group")

@@ -572,8 +572,7 @@ def topk_merge(val, idx):
 # ------------------------------------------------------------------------------------------------
 # dense layers
 # ------------------------------------------------------------------------------------------------
-def _vp(ptr):
-    return C.c_void_p(ptr)
+from .launch import vp as _vp       # noqa: E402  (the single pointer conversion: tensor | int address | None)
 
 
 # Weight gradients of thin layers (a contraction over <= 128 batch rows) are leaves of the backward pass: nothing but the optimizer
