@@ -167,6 +167,12 @@ SIGNATURES = {
     "evae_causal_attn_lds_bytes": (_z, [_i, _i]),
     "evae_causal_attn_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _f, _q, _q, _p, _p, _p]),
     "evae_causal_attn_bwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _q, _q, _p, _p, _p, _p, _p]),
+    "evae_pixel_decode_images_per_block": (_i, []),
+    "evae_pixel_decode_table_len": (_i, []),
+    "evae_pixel_decode_cache_floats": (_z, []),
+    "evae_pixel_decode_lds_bytes": (_z, []),
+    "evae_pixel_decode_slot_floats": (_i, [_i]),
+    "evae_pixel_decode": (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
     "evae_elu_dropout_fwd": (_i, [_p, _z, _f, _q, _q, _p, _p]),
     "evae_elu_dropout_bwd": (_i, [_p, _p, _z, _f, _q, _q, _p, _p]),
     "evae_glu_res_fwd": (_i, [_p, _p, _l, _i, _p, _p]),

@@ -2570,3 +2570,205 @@ class GluResFn(torch.autograd.Function):
 
 def glu_res(ab, x):
     return GluResFn.apply(ab, x)
+
+
+# ------------------------------------------------------------------------------------------------
+# cached ancestral sampler of the pixelcnn decoder: csrc/evae_pixel_decode.hip
+# ------------------------------------------------------------------------------------------------
+PIXEL_DECODE_MAGIC = 0x50584443
+_PD_BLOCK = "pixelcnn.blocks.0."
+
+
+def _pd_slots():
+    """The slots of the packed buffer in the order of csrc/evae_pixel_decode.hip::PdSlot: (name, modules, kind, join).  kind 'w':
+    the weight as [inputs][outputs] with the inputs ordered (filter row, filter column, channel); 'w7': the same of a causal 3 x 3
+    filter, its 7 live taps only; 'b': the bias; 'buffer': a buffer as it is.  Several modules are joined along the inputs ('rows')
+    or the outputs ('cols')."""
+    hor, ver = "pixelcnn.horizontal.conv.conv", "pixelcnn.vertical.conv.conv"
+    s = [("in_w", [hor, ver], "w", "rows"), ("hor_b", [hor], "b", "cols"), ("ver_b", [ver], "b", "cols")]
+    for r in range(4):
+        for c in ("conv1", "conv2"):
+            m = "%sresblocks.%d.%s.conv.conv" % (_PD_BLOCK, r, c)
+            s += [("res%d_%s_w" % (r, c), [m], "w7", "rows"), ("res%d_%s_b" % (r, c), [m], "b", "cols")]
+    for blk in ("key_resblock", "query_resblock"):
+        for c in ("conv1", "conv2"):
+            m = "%s%s.%s.conv" % (_PD_BLOCK, blk, c)
+            s += [("%s_%s_w" % (blk, c), [m], "w", "rows"), ("%s_%s_b" % (blk, c), [m], "b", "cols")]
+    att = _PD_BLOCK + "causal_attention."
+    s += [("attn_q_w", [att + "query"], "w", "rows"), ("attn_q_b", [att + "query"], "b", "cols"),
+          ("attn_kv_w", [att + "key", att + "value"], "w", "cols"), ("attn_kv_b", [att + "key", att + "value"], "b", "cols")]
+    o = _PD_BLOCK + "out_resblock."
+    s += [("out_res_conv1_aux_w", [o + "conv1.conv", o + "aux_conv.conv"], "w", "rows"), ("out_res_conv1_b", [o + "conv1.conv"], "b", "cols"),
+          ("out_res_aux_b", [o + "aux_conv.conv"], "b", "cols"), ("out_res_conv2_w", [o + "conv2.conv"], "w", "rows"),
+          ("out_res_conv2_b", [o + "conv2.conv"], "b", "cols")]
+    s += [("out_w", ["pixelcnn.out.1.conv"], "w", "rows"), ("out_b", ["pixelcnn.out.1.conv"], "b", "cols"),
+          ("mean_w", ["p_x_mean.conv"], "w", "rows"), ("mean_b", ["p_x_mean.conv"], "b", "cols"),
+          ("background", ["pixelcnn"], "buffer", "rows")]
+    return s
+
+
+def _pd_weight_names(shapes, module):
+    """state-dict names behind the weight of `module`: weight_g and weight_v of a weight-normed one, else weight"""
+    if module + ".weight_v" in shapes:
+        return [module + ".weight_g", module + ".weight_v"]
+    return [module + ".weight"]
+
+
+def _numel(shape):
+    n = 1
+    for d in shape:
+        n *= int(d)
+    return n
+
+
+def pixel_decode_images_per_block():
+    """images one workgroup of the decode kernel owns (a launch of B images takes ceil(B / this) workgroups)"""
+    return int(_lib.load().evae_pixel_decode_images_per_block())
+
+
+def pixel_decode_layout(shapes, n_head=8):
+    """The packed buffer of ops.pixel_decode for a decoder whose state dict has `shapes` {name: shape} (names 'pixelcnn.*' and
+    'p_x_mean.conv.*'): {'table': the ints the kernel's entry point takes (header, then one float offset per slot), 'total': floats
+    of the buffer, 'entries': one {'slot', 'offset', 'floats', 'shape', 'sources': {state-dict name: elements}} per slot}.  Every
+    slot starts on a multiple of 4 floats, the biases form one block at the end (the kernel keeps it in LDS); outputs are padded to a multiple of 4 (the mean head: 1 -> 4).  Host arithmetic only."""
+    entries = []
+    for name, modules, kind, join in _pd_slots():
+        sources, rows, cols = {}, 0, 0
+        for m in modules:
+            if kind == "buffer":
+                names = [m + ".background"]
+                shp = shapes[names[0]]
+                r, c = _numel(shp[:2]), _numel(shp[2:])
+            elif kind == "b":
+                names = [m + ".bias"]
+                r, c = 1, _numel(shapes[names[0]])
+            else:
+                names = _pd_weight_names(shapes, m)
+                shp = shapes[names[-1]]
+                c, r = int(shp[0]), _numel(shp[1:])
+                if kind == "w7":
+                    if tuple(shp[2:]) != (3, 3):
+                        raise _lib.EvaeError("pixel_decode: %s is not a 3 x 3 filter" % m)
+                    r = r // 9 * 7
+            for n in names:
+                sources[n] = _numel(shapes[n])
+            if join == "rows" or kind == "buffer":
+                if cols not in (0, c):
+                    raise _lib.EvaeError("pixel_decode: the outputs of %s do not match" % (modules,))
+                rows, cols = rows + r, c
+            else:
+                if rows not in (0, r):
+                    raise _lib.EvaeError("pixel_decode: the inputs of %s do not match" % (modules,))
+                rows, cols = r, cols + c
+        if kind != "buffer":
+            cols = (cols + 3) // 4 * 4
+        entries.append(dict(slot=name, offset=None, floats=rows * cols, shape=(rows, cols), kind=kind, join=join, modules=modules,
+                            sources=sources))
+    off = 0
+    for bias in (False, True):                  # the matrices (and the background) first, then all biases as one block
+        for e in entries:
+            if (e["kind"] == "b") == bias:
+                e["offset"] = off
+                off += (e["floats"] + 3) // 4 * 4
+    attn = int(shapes[_PD_BLOCK + "causal_attention.query.weight_v"][0])
+    n_res = len([k for k in shapes if k.startswith(_PD_BLOCK + "resblocks.") and k.endswith(".conv1.conv.conv.bias")])
+    bg = shapes["pixelcnn.background"]
+    header = [PIXEL_DECODE_MAGIC, int(shapes["pixelcnn.horizontal.conv.conv.bias"][0]),
+              int(shapes[_PD_BLOCK + "resblocks.0.conv1.conv.conv.bias"][0]), int(bg[2]), int(bg[3]), n_res, int(n_head), attn // int(n_head), off]
+    return dict(table=header + [e["offset"] for e in entries], total=off, entries=entries)
+
+
+class PixelDecodeWeights:
+    """the packed weights of one generation: `buffer` (device floats), `table` (host ints), `entries` (pixel_decode_layout)"""
+
+    def __init__(self, buffer, table, entries):
+        self.buffer, self.table, self.entries = buffer, list(table), entries
+
+
+class PixelDecodeCache:
+    """what ops.pixel_decode keeps between the pixels of B images: `planes` [B, evae_pixel_decode_cache_floats()] and the means
+    written so far, `mean` [B, 784] (zeros where no launch has been yet)"""
+
+    def __init__(self, B, device):
+        self.planes = torch.zeros((B, int(_lib.load().evae_pixel_decode_cache_floats())), device=device)
+        self.mean = torch.zeros((B, 784), device=device)
+
+
+def pixel_decode_pack(pixelsnail, mean_head):
+    """PixelSNAIL module + the mean head (models/PixelCNN.py: self.pixelcnn, self.p_x_mean) -> PixelDecodeWeights, once per generation:
+    the causal filters are masked as on every forward call, all weight-normed filters come from ONE weight_norm_set launch, and
+    every matrix is stored transposed in the layout of pixel_decode_layout."""
+    lib = _lib.load()
+    with torch.no_grad():
+        named = {"pixelcnn" + ("." + n if n else ""): m for n, m in pixelsnail.named_modules()}
+        named["p_x_mean.conv"] = mean_head.conv
+        state = {"pixelcnn." + k: v for k, v in pixelsnail.state_dict().items()}
+        state.update({"p_x_mean.conv." + k: v for k, v in mean_head.conv.state_dict().items()})
+        _need_cuda(*state.values())
+        for m in named.values():
+            if hasattr(m, "mask_weight"):
+                m.mask_weight()
+        normed = [n for n, m in named.items() if hasattr(m, "weight_v") and hasattr(m, "weight_g")]
+        ws = weight_norm_set([(named[n].weight_v.detach(), named[n].weight_g.detach()) for n in normed])
+        weight = dict(zip(normed, ws))
+        n_head = named[_PD_BLOCK + "causal_attention"].n_head
+        lay = pixel_decode_layout({k: tuple(v.shape) for k, v in state.items()}, n_head=n_head)
+        if len(lay["table"]) != lib.evae_pixel_decode_table_len():
+            raise _lib.EvaeError("pixel_decode_pack: the layout has %d table entries, the kernel takes %d"
+                                 % (len(lay["table"]), lib.evae_pixel_decode_table_len()))
+        buf = torch.zeros(lay["total"], device=ws[0].device)
+        for s, e in enumerate(lay["entries"]):
+            if e["floats"] != lib.evae_pixel_decode_slot_floats(s):
+                raise _lib.EvaeError("pixel_decode_pack: %s holds %d floats, the kernel is built for %d (another decoder configuration)"
+                                     % (e["slot"], e["floats"], lib.evae_pixel_decode_slot_floats(s)))
+            parts = []
+            for m in e["modules"]:
+                if e["kind"] == "buffer":
+                    parts.append(state[m + ".background"].float().reshape(e["shape"]))
+                elif e["kind"] == "b":
+                    parts.append(state[m + ".bias"].float().reshape(1, -1))
+                else:
+                    w = weight[m] if m in weight else state[m + ".weight"].float()
+                    if w.dim() == 2:
+                        w = w.view(w.shape[0], w.shape[1], 1, 1)
+                    wt = w.permute(2, 3, 1, 0).reshape(-1, w.shape[1], w.shape[0])           # [taps][inputs][outputs]
+                    if e["kind"] == "w7":
+                        wt = wt[:7]
+                    parts.append(wt.reshape(-1, w.shape[0]))
+            mat = torch.cat(parts, 0 if (e["join"] == "rows" or e["kind"] == "buffer") else 1)
+            rows, cols = e["shape"]
+            out = buf[e["offset"]:e["offset"] + rows * cols].view(rows, cols)
+            out[:, :mat.shape[1]] = mat
+        return PixelDecodeWeights(buf, lay["table"], lay["entries"])
+
+
+def pixel_decode(packed, latent, x, u=None, t0=0, t1=784, cache=None):
+    """The eval-mode pixelcnn decoder at the pixels t0 <= t < t1 in raster order, one launch (csrc/evae_pixel_decode.hip).
+    packed: pixel_decode_pack(...); latent [B, 2, 28, 28]; x [B, 784] float32; u [B, 784] uniforms or None; cache: the
+    PixelDecodeCache of earlier launches over the same images (None: a fresh one, for t0 = 0).
+    Returns (mean, x, cache): mean = cache.mean [B, 784], written at the pixels of every launch so far.  With u, x[:, t] is set IN
+    PLACE to (u[:, t] < mean[:, t]) before pixel t + 1 is evaluated (x must then be a contiguous float32 tensor); without u the
+    call is teacher-forced and x is only read.  No gradients: raises if an input requires grad while grad is enabled."""
+    lib = _lib.load()
+    ts = (packed.buffer, latent, x, u)
+    _need_cuda(*ts)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts):
+        raise _lib.EvaeError("pixel_decode is a no-grad operator: an input requires grad (call it under torch.no_grad())")
+    B = x.shape[0]
+    if x.dim() != 2 or x.shape[1] != 784 or tuple(latent.shape) != (B, 2, 28, 28) or (u is not None and u.shape != x.shape):
+        raise _lib.EvaeError("pixel_decode: x and u must be [B, 784] and latent [B, 2, 28, 28]")
+    if u is not None:
+        if x.dtype != torch.float32 or not x.is_contiguous():
+            raise _lib.EvaeError("pixel_decode: sampling writes x in place: it must be a contiguous float32 tensor")
+        u = _f32(u)
+    else:
+        x = _f32(x)
+    latent = _f32(latent)
+    if cache is None:
+        cache = PixelDecodeCache(B, x.device)
+    if cache.mean.shape[0] != B or cache.planes.shape[0] != B:
+        raise _lib.EvaeError("pixel_decode: the cache was made for %d images, not %d" % (cache.mean.shape[0], B))
+    table = (C.c_int * len(packed.table))(*packed.table)
+    _lib.check(lib.evae_pixel_decode(_p(packed.buffer), table, len(packed.table), _p(latent), _p(x), _p(u), _p(cache.mean), _p(cache.planes),
+                                     B, int(t0), int(t1), _stream()), "evae_pixel_decode")
+    return cache.mean, x, cache

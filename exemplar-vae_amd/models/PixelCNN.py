@@ -6,6 +6,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from evae import ops
 from models.AbsHModel import BaseHModel
 from utils.nn import Conv2d, GatedConv2d, GatedConvStack, GatedDense, NonLinear, PixelSNAIL
 
@@ -76,8 +77,25 @@ class VAE(BaseHModel):
         """Ancestral sampling, pixel by pixel in raster order (reference :91-120, binary branch): the mean of pixel (i, j)
         given the pixels drawn so far, one Bernoulli draw from it.  Returns the means of the last pass.  The network is causal:
         the means of rows <= i depend on input rows <= i only, so pass (i, j) runs the decoder on the first i + 1 rows; the last
-        pass sees every row, and its result is the reference's."""
+        pass sees every row, and its result is the reference's.
+
+        args.pixelcnn_sampler = 'cached' (default 'passes': the 784 passes described above), in eval mode: the same ancestral sampling in ONE launch
+        of evae.ops.pixel_decode, which evaluates one pixel of every layer at a time over cached activations.  It draws its uniforms
+        with one torch.rand(B, 784) where the passes call torch.bernoulli 784 times, so equal seeds give different, equally
+        distributed images.  The kernel is the eval-mode network: in training mode (self.training) the reference's dropout stays
+        active during generation, and the flag is ignored -- the passes run."""
         c, hh, ww = self.args.input_size
+        sampler = getattr(self.args, 'pixelcnn_sampler', 'passes')
+        if sampler not in ('passes', 'cached'):
+            raise ValueError("pixelcnn_sampler must be 'passes' or 'cached' (got %r)" % (sampler,))
+        if sampler == 'cached' and not self.training:
+            with torch.no_grad():
+                latent = self._decoder_images(z1, z2)
+                u = torch.rand(z1.size(0), c * hh * ww, device=z1.device)
+                packed = ops.pixel_decode_pack(self.pixelcnn, self.p_x_mean)
+                x = torch.zeros((z1.size(0), c * hh * ww), device=z1.device)
+                mean, _, _ = ops.pixel_decode(packed, latent, x, u=u)
+                return mean
         with torch.no_grad():
             x = torch.zeros((z1.size(0), c, hh, ww), device=z1.device)
             latent = self._decoder_images(z1, z2)

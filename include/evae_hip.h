@@ -548,6 +548,30 @@ int evae_elu_dropout_bwd(const float* dy, const float* x, size_t n, float p_drop
 int evae_glu_res_fwd(const float* ab, const float* x, int64_t M, int C, float* out, evae_stream_t stream);
 int evae_glu_res_bwd(const float* dout, const float* ab, int64_t M, int C, float* dab, evae_stream_t stream);
 
+/* Cached ancestral sampler of the `pixelcnn` decoder (csrc/evae_pixel_decode.hip): one persistent kernel evaluates the eval-mode
+ * PixelSNAIL([28, 28], 64, 64, 3, 1, 4, 64) + the 1x1 mean head with its sigmoid for the pixels t0 <= t < t1 in raster order, one
+ * pixel of every layer at a time, for B images; a workgroup owns evae_pixel_decode_images_per_block() images.
+ *   packed   the weights of this pass (weight-normalised), each matrix transposed to [inputs][outputs]; `table` (HOST memory,
+ *            evae_pixel_decode_table_len() ints) = magic, channel, res_channel, height, width, n_res_block, heads, head width, total
+ *            floats, then one float offset (a multiple of 4) per slot in the order of csrc/evae_pixel_decode.hip::PdSlot, slot s
+ *            holding evae_pixel_decode_slot_floats(s) floats; the bias slots form one block of at most 2048 floats (kept in LDS).
+ *            evae/ops.py::pixel_decode_layout writes both.
+ *   latent   [B, 2, 28, 28] the two latent images;  x [B, 784];  u [B, 784] uniforms or NULL;  mean [B, 784]
+ *   cache    [B, evae_pixel_decode_cache_floats()], 16-byte aligned, zeros before the first pixel: 8 planes [784][64] (per residual
+ *            block the ELU of its input and of its conv1 output), then K and V [8][784][4].  Pixel t reads positions < t, writes t.
+ * mean[:, t] is written for every pixel of the range.  With u: x[:, t] = u[:, t] < mean[:, t] ? 1 : 0, written before pixel t + 1
+ * is evaluated.  Without u the call is teacher-forced: x is read only.  fp32 throughout, no atomics, every sum in a fixed order:
+ * runs are bit-identical, and [0, 784) in several calls over one cache equals one call.  Dropout does not exist here.
+ * Refused (EVAE_EINVAL, nothing launched): a table of other channel counts, image sizes, block / head counts, offsets outside the
+ * buffer, scattered bias slots, t0 > t1, t1 > 784, null or unaligned pointers.  B == 0 and t0 == t1 return at once. */
+int evae_pixel_decode_images_per_block(void);
+int evae_pixel_decode_table_len(void);
+size_t evae_pixel_decode_cache_floats(void);
+size_t evae_pixel_decode_lds_bytes(void);
+int evae_pixel_decode_slot_floats(int slot);
+int evae_pixel_decode(const float* packed, const int* table, int table_len, const float* latent, float* x, const float* u, float* mean,
+                      float* cache, int B, int t0, int t1, evae_stream_t stream);
+
 /* Window convolutions over pre-split pixel images (csrc/evae_conv_win.h): the gated layers BETWEEN two layers of a convolutional
  * encoder stack (reference utils/nn.py:72-97, models/convHVAE_2level.py:21-46), whose activations then never exist as fp32
  * tensors.  A "pixel image" holds an activation [pixels x channels] (channels % 16 == 0) as three bf16 planes per 16 pixels x 16
