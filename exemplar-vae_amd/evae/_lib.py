@@ -20,6 +20,14 @@ _u = C.c_uint
 _q = C.c_uint64
 
 
+def vp(v):
+    """tensor | int address | None -> c_void_p | None: the single pointer conversion (evae.launch and evae.ops both take it from
+    here, so neither has to be imported before the other)"""
+    if v is None:
+        return None
+    return C.c_void_p(v if isinstance(v, int) else v.data_ptr())
+
+
 class ConvDesc(C.Structure):
     """evae_conv_desc_t"""
     _fields_ = [(n, C.c_int) for n in ("N", "C", "H", "W", "Co", "KH", "KW", "stride", "pad")]

@@ -22,7 +22,7 @@ from types import SimpleNamespace
 import torch
 
 from . import _lib, handoff, ops
-from .launch import Launcher, beta_args, ptr, vp, wgrad_jobs
+from .launch import Launcher, beta_args, vp, wgrad_jobs
 
 ACT_NONE, ACT_SIGMOID = ops.ACT_NONE, ops.ACT_SIGMOID
 LV_LO, LV_HI = -6.0, 2.0           # the Hardtanh of q_z_logvar (models/VAE.py)
@@ -171,7 +171,7 @@ def _bwd_latent(k, st, p):
 def _bwd_weights(k, jobs):
     """jobs: (dy, M, N, ldy, x, K, ldx, dw, db).  Those the grouped kernel takes (a contraction over <= 128 rows, widths in
     fours) go out six to a launch; the rest one by one."""
-    fits = [j[1] <= 128 and all(v % 4 == 0 for v in (j[2], j[3], j[5], j[6])) and all(ptr(t) % 16 == 0 for t in (j[0], j[4], j[7]))
+    fits = [j[1] <= 128 and all(v % 4 == 0 for v in (j[2], j[3], j[5], j[6])) and all(vp(t).value % 16 == 0 for t in (j[0], j[4], j[7]))
             for j in jobs]
     grouped = [j for j, ok in zip(jobs, fits) if ok]
     for i in range(0, len(grouped), 6):

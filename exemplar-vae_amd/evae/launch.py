@@ -1,8 +1,11 @@
-"""The raw-launch layer of the fused training steps (evae/fused_vae.py, evae/fused_std.py): the one pointer conversion, the
-launcher over the dense entry points of the C ABI, the two job-table fillers, the beta pair.  No autograd, caller-owned outputs.
+"""The raw-launch layer of the fused training steps (evae/fused_vae.py, evae/fused_std.py) and of the dense autograd operators
+of evae/ops.py: the launcher over the dense entry points of the C ABI, the two job-table fillers, the beta pair (the one pointer
+conversion, vp, is evae/_lib.py's).  No autograd, caller-owned outputs.
 
-The steps built on it are stage functions over one per-step state object.  Every change to them keeps four invariants; they are
-held by tests/test_gpu_step_trace.py (what a step issues, record for record, against a recorded golden), not by a reader's eye:
+The fused steps are stage functions over one per-step state object; the modular operators (GatedDenseFn, LinearFn, the heads'
+backward, the deferred weight gradients) are torch.autograd.Functions that build a Launcher where they run.  Every change to
+either keeps four invariants; they are held by tests/test_gpu_step_trace.py (what a step or an operator issues, record for record,
+against the recorded goldens g28 and g29), not by a reader's eye:
 
 * ISSUE ORDER IS BEHAVIOUR.  The order launches, event records and stream waits are issued in is the order the captured hipGraph
   starts them in: the leaves of fused_vae's backward pass issued elsewhere replayed at 0.82-1.2 ms against 0.66.  Stages are
@@ -14,23 +17,21 @@ held by tests/test_gpu_step_trace.py (what a step issues, record for record, aga
   keeps no tensor of its own: what it allocates goes on the step state -- a pass's temporaries on st.fwd / st.bwd, cleared where
   that pass returns; what the backward pass needs on the state itself, dropped where the backward pass returns.
 * MODULE-LEVEL SWITCHES KEEP THEIR NAMES AND THEIR READ TIME: import-time constants stay import-time, per-call reads
-  (node_merge(), the os.environ reads inside the passes) stay per-call.  evae/graph.py and tools/ read them by name."""
+  (node_merge(), the os.environ reads inside the passes) stay per-call.  evae/graph.py and tools/ read them by name.
+
+In evae/ops.py the same four bind the dense operators: the order of an operator's launches, size queries and allocations, the
+stream current at each, the tensors a backward keeps until it returns, and the module attributes tests and bench.py assign to
+(ops.PROBE, ops._DEFER, ops._ws, ...: they stay on evae.ops and are read there at call time).  Two more come with them: WHICH
+launches ops.probed brackets, and under which name, is behaviour (bench.py builds its roofline from those records) -- hence the
+*_call methods below, the launch without the bracket; and no entry point is kept bound across calls (`self.lib.evae_x` is looked
+up at each launch): the recorder and _lib.count_calls patch the names on the loaded library object."""
 import ctypes as C
 import os
 
 import torch
 
-from . import _lib
-
-
-def vp(v):
-    """tensor | int address | None -> c_void_p | None: the single pointer conversion"""
-    if v is None:
-        return None
-    return C.c_void_p(v if isinstance(v, int) else v.data_ptr())
-
-
-from . import ops       # noqa: E402  (evae.ops takes vp from here: it has to exist before ops is imported)
+from . import _lib, ops
+from ._lib import vp
 
 
 def beta_args(beta):
@@ -40,17 +41,15 @@ def beta_args(beta):
     return None, float(beta)
 
 
-def ptr(t):
-    return t if isinstance(t, int) else t.data_ptr()
-
-
 def wgrad_jobs(jobs):
-    """(dy, M, N, ldy, x, K, ldx, dw, db) per job -> (evae_wgrad_job_t array as c_void_p, count, the array: keep it until the
-    launch is issued).  Which jobs share a launch is the caller's rule."""
+    """(dy, M, N, ldy, x, K, ldx, dw, db[, accumulate]) per job -> (evae_wgrad_job_t array as c_void_p, count, the array: keep it
+    until the launch is issued).  accumulate = 1: dw += the product, db += its column sums (default 0).  Which jobs share a
+    launch is the caller's rule."""
     arr = (_lib.WgradJob * len(jobs))()
-    for a, (dy, M, N, ldy, x, K, ldx, dw, db) in zip(arr, jobs):
-        a.dy, a.x, a.dw, a.db = ptr(dy), ptr(x), ptr(dw), ptr(db)
+    for a, (dy, M, N, ldy, x, K, ldx, dw, db, *acc) in zip(arr, jobs):
+        a.dy, a.x, a.dw, a.db = vp(dy), vp(x), vp(dw), vp(db)
         a.M, a.N, a.K, a.ldy, a.ldx = M, N, K, ldy, ldx
+        a.accumulate = acc[0] if acc else 0
     return C.cast(arr, C.c_void_p), len(jobs), arr
 
 
@@ -59,7 +58,7 @@ def wgrad_finish_jobs(jobs):
     arr = (_lib.WgradFinishJob * len(jobs))()
     for a, (byte_rows, M, N, K, ldy, ldx, x_scale, dw, db, ws) in zip(arr, jobs):
         a.byte_rows, a.M, a.N, a.K, a.ldy, a.ldx = byte_rows, M, N, K, ldy, ldx
-        a.x_scale, a.dw, a.db, a.ws, a.ws_bytes = x_scale, ptr(dw), ptr(db), ws.data_ptr(), ws.numel()
+        a.x_scale, a.dw, a.db, a.ws, a.ws_bytes = x_scale, vp(dw), vp(db), vp(ws), ws.numel()
     return C.cast(arr, C.c_void_p), len(jobs), arr
 
 
@@ -96,45 +95,65 @@ class Launcher:
     def _pipe(self, M, N, gated, flops, fits=True):
         return ops.gemm_pipe(M, N, gated, flops) if (fits and self.pipes) else (None, "fp32-mfma")
 
+    # <name>_call: the launch, its workspace taken now, as a closure -- for the callers whose launch ops.probed does not bracket
+    # (the operators of evae/ops.py outside GatedDenseFn.forward); <name>: the same launch inside its bracket
+
+    def gated_fwd_call(self, x, rows, M, K, ldx, wh, bh, wg, bg, N, out, h, s):
+        w = self.ws("fwd", self.lib.evae_dense_fwd_workspace_bytes(M, K, N, 1))
+        return lambda: _lib.check(self.lib.evae_gated_dense_fwd(vp(x), vp(rows), M, K, ldx, vp(wh), vp(bh), vp(wg), vp(bg), N, vp(out),
+                                                                vp(h), vp(s), vp(w), w.numel(), self.st), "gated_fwd")
+
     def gated_fwd(self, x, rows, M, K, ldx, wh, bh, wg, bg, N, out, h, s):
-        nb = self.lib.evae_dense_fwd_workspace_bytes(M, K, N, 1)
-        w = self.ws("fwd", nb)
+        call = self.gated_fwd_call(x, rows, M, K, ldx, wh, bh, wg, bg, N, out, h, s)
         ex_, pipe_ = self._pipe(M, N, True, 2.0 * M * K * 2 * N, rows is None)
         ops.probed("gated_dense_fwd M=%d K=%d N=%d%s" % (M, K, N, " (row gather)" if rows is not None else ""), 2.0 * M * K * 2 * N,
-                   lambda: _lib.check(self.lib.evae_gated_dense_fwd(vp(x), vp(rows), M, K, ldx, vp(wh), vp(bh), vp(wg), vp(bg),
-                                                                    N, vp(out), vp(h), vp(s), vp(w), w.numel(), self.st),
-                                      "gated_fwd"), executed=ex_, pipe=pipe_)
+                   call, executed=ex_, pipe=pipe_)
 
-    def linear_fwd(self, x, M, K, ldx, w_, b, N, act, lo, hi, y, pre):
-        nb = self.lib.evae_dense_fwd_workspace_bytes(M, K, N, 0)
-        w = self.ws("fwd", nb)
-        _lib.check(self.lib.evae_linear_fwd(vp(x), None, M, K, ldx, vp(w_), vp(b), N, act, lo, hi, vp(y), vp(pre),
+    def linear_fwd(self, x, M, K, ldx, w_, b, N, act, lo, hi, y, pre, rows=None):
+        w = self.ws("fwd", self.lib.evae_dense_fwd_workspace_bytes(M, K, N, 0))
+        _lib.check(self.lib.evae_linear_fwd(vp(x), vp(rows), M, K, ldx, vp(w_), vp(b), N, act, lo, hi, vp(y), vp(pre),
                                             vp(w), w.numel(), self.st), "linear_fwd")
 
+    def bwd_data_call(self, dy1, w1, dy2, w2, M, N, ldy, K, out_prev, s_prev, out, dg, ldo, wT=None):
+        """dx [M x K] = dy1 W1 (+ dy2 W2); with out_prev / s_prev (forward output and gate of the layer below) the gate derivative
+        of that layer is applied in the epilogue and (dh, dg) are written instead.  wT: the transposed weights prepared by the
+        step's head launch, or None (then evae_dense_bwd_data_wt IS evae_dense_bwd_data: both are dense_bwd_data_core,
+        csrc/evae_dense.hip)"""
+        w = self.ws("dgrad", self.lib.evae_dense_bwd_data_workspace_bytes(M, N, K, 2 if dy2 is not None else 1))
+        return lambda: _lib.check(self.lib.evae_dense_bwd_data_wt(vp(dy1), vp(w1), vp(dy2), vp(w2), M, N, ldy, K, vp(out_prev),
+                                                                  vp(s_prev), vp(out), vp(dg), ldo, vp(wT), vp(w), w.numel(),
+                                                                  self.st), "bwd_data")
+
     def bwd_data(self, dy1, w1, dy2, w2, M, N, ldy, K, out_prev, s_prev, out, dg, ldo, wT=None):
-        """wT: the transposed weights prepared by the step's head launch, or None (then evae_dense_bwd_data_wt IS
-        evae_dense_bwd_data: both are dense_bwd_data_core, csrc/evae_dense.hip)"""
-        nb = self.lib.evae_dense_bwd_data_workspace_bytes(M, N, K, 2 if dy2 is not None else 1)
-        w = self.ws("dgrad", nb)
+        call = self.bwd_data_call(dy1, w1, dy2, w2, M, N, ldy, K, out_prev, s_prev, out, dg, ldo, wT)
         fl_ = 2.0 * M * N * K * (2 if dy2 is not None else 1)
         ex_, pipe_ = self._pipe(M, K, False, fl_, N % 4 == 0 and ldy % 4 == 0)
         ops.probed("dense_bwd_data M=%d N=%d%s K=%d%s" % (M, N, "+%d" % N if dy2 is not None else "", K,
                                                           " (gate-backward epilogue)" if out_prev is not None else ""), fl_,
-                   lambda: _lib.check(self.lib.evae_dense_bwd_data_wt(vp(dy1), vp(w1), vp(dy2), vp(w2), M, N, ldy, K, vp(out_prev),
-                                                                      vp(s_prev), vp(out), vp(dg), ldo, vp(wT), vp(w), w.numel(),
-                                                                      self.st), "bwd_data"), executed=ex_, pipe=pipe_)
+                   call, executed=ex_, pipe=pipe_)
+
+    def gated_bwd(self, dout, ldd, gout, s, M, N, wh, wg, K, dpre, dx):
+        """a gated layer's gate derivative and data gradient as one entry point (one launch for batch-sized row counts): fills
+        dpre = [dh | dg] [M x 2N] and dx = dh Wh + dg Wg [M x K]"""
+        w = self.ws("dgrad", self.lib.evae_dense_bwd_data_workspace_bytes(M, N, K, 2))
+        _lib.check(self.lib.evae_gated_dense_bwd(vp(dout), ldd, vp(gout), vp(s), M, N, vp(wh), vp(wg), K, vp(dpre), 2 * N,
+                                                 vp(dx), K, vp(w), w.numel(), self.st), "gated_bwd")
+
+    def bwd_weight_call(self, dy, M, N, ldy, x, rows, K, ldx, dw, db, ws_name="wgrad"):
+        """dw [N x K] = dy^T x(rows), db [N] = column sums of dy: the split-K GEMM and its finish"""
+        w = self.ws(ws_name, self.lib.evae_dense_bwd_weight_workspace_bytes(M, N, K))
+        return lambda: _lib.check(self.lib.evae_dense_bwd_weight(vp(dy), M, N, ldy, vp(x), vp(rows), K, ldx, vp(dw), vp(db), 0,
+                                                                 vp(w), w.numel(), self.st), "bwd_weight")
 
     def bwd_weight(self, dy, M, N, ldy, x, rows, K, ldx, dw, db, phase=0, ws_name="wgrad", finish_on=None):
         """phase 1 / 2: the split-K GEMM and its finish as separate calls (finish_on = the launcher whose stream runs it)"""
-        nb = self.lib.evae_dense_bwd_weight_workspace_bytes(M, N, K)
-        w = self.ws(ws_name, nb)
         if phase == 0:
             # (a narrow output over many rows -- the heads' [40 x 300] over all C + B rows -- streams its operands once: an HBM entry)
             ops.probed("dense_bwd_weight M=%d N=%d K=%d (+db, split-K GEMM + finish)" % (M, N, K), 2.0 * M * N * K,
-                       hbm_bytes=(4.0 * M * (N + K)) if (N <= 64 and M >= 2048 and rows is None) else None, fn=
-                       lambda: _lib.check(self.lib.evae_dense_bwd_weight(vp(dy), M, N, ldy, vp(x), vp(rows), K, ldx, vp(dw),
-                                                                         vp(db), 0, vp(w), w.numel(), self.st), "bwd_weight"))
+                       hbm_bytes=(4.0 * M * (N + K)) if (N <= 64 and M >= 2048 and rows is None) else None,
+                       fn=self.bwd_weight_call(dy, M, N, ldy, x, rows, K, ldx, dw, db, ws_name))
         else:
+            w = self.ws(ws_name, self.lib.evae_dense_bwd_weight_workspace_bytes(M, N, K))
             st = self.st if finish_on is None else finish_on.st
             call = lambda: _lib.check(self.lib.evae_dense_bwd_weight_phased(vp(dy), M, N, ldy, vp(x), vp(rows), K, ldx, vp(dw),
                                                                             vp(db), 0, vp(w), w.numel(), phase, st), "bwd_weight_phased")
@@ -145,6 +164,6 @@ class Launcher:
                 call()
 
     def bwd_weight_group(self, jobs):
-        """ONE launch for up to six thin weight gradients (evae_dense_bwd_weight_group)"""
+        """ONE launch for up to six thin weight gradients (evae_dense_bwd_weight_group; jobs as wgrad_jobs takes them)"""
         arr, n, _keep = wgrad_jobs(jobs)
         _lib.check(self.lib.evae_dense_bwd_weight_group(arr, n, self.st), "bwd_weight_group")

@@ -7,7 +7,8 @@ import os
 
 import torch
 
-from . import _lib, handoff
+from . import _lib, handoff, launch
+from ._lib import vp
 
 ACT_NONE, ACT_SIGMOID, ACT_HARDTANH = 0, 1, 2
 TOPK_SQRT = 1
@@ -120,8 +121,7 @@ def _workspace(name, nbytes, device):
     return buf
 
 
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
+_p = _vp = vp       # (the names this file, tests/ and tools/ call the one pointer conversion by)
 
 
 def _stream():
@@ -572,9 +572,9 @@ def topk_merge(val, idx):
 # ------------------------------------------------------------------------------------------------
 # dense layers
 # ------------------------------------------------------------------------------------------------
-from .launch import vp as _vp       # noqa: E402  (the single pointer conversion: tensor | int address | None)
-
-
+# The launches of this section go through evae/launch.py's Launcher (workspace names, entry points, the probe's names), built
+# where the operator runs: its stream is the one current there.
+#
 # Weight gradients of thin layers (a contraction over <= 128 batch rows) are leaves of the backward pass: nothing but the optimizer
 # reads them, yet each one is a launch on the chain of data gradients (8-15 us apiece in the 2-level model's step, a dozen of them).
 # Inside `with ops.deferred_wgrads():` (the captured step and utils.training put it around loss.backward()) such a gradient is only
@@ -591,23 +591,19 @@ _DEFER_ON = os.environ.get("EVAE_DEFER_WGRAD", "1") != "0"
 def _flush_wgrads(jobs, everyone_waits=False):
     """launch the pending jobs, grouped by the stream their layer's backward ran on; the current stream (everyone_waits: every
     registered stream) then waits for those launches"""
-    lib = _lib.load()
     cur = torch.cuda.current_stream()
     by_stream = {}
     for j in jobs:
         by_stream.setdefault(j[8].cuda_stream, (j[8], []))[1].append(j)
     for st, js in by_stream.values():
+        k = launch.Launcher(js[0][0].device, stream=st)
         for i in range(0, len(js), 6):
             part = js[i:i + 6]
-            arr = (_lib.WgradJob * len(part))()
-            for a, (dy, M, N, x, K, dw, db, _key, _st, made_ev) in zip(arr, part):
-                a.dy = dy.data_ptr(); a.x = x.data_ptr(); a.dw = dw.data_ptr(); a.db = db.data_ptr()
-                a.M, a.N, a.K, a.ldy, a.ldx = M, N, K, dy.stride(0), x.stride(0)
-                if made_ev is not None:            # dw += ...: behind the launch that wrote the other application's gradient
-                    a.accumulate = 1
-                    st.wait_event(made_ev)
-            _lib.check(lib.evae_dense_bwd_weight_group(C.cast(arr, C.c_void_p), len(part), C.c_void_p(st.cuda_stream)),
-                       "evae_dense_bwd_weight_group(deferred)")
+            for j in part:
+                if j[9] is not None:               # dw += ...: behind the launch that wrote the other application's gradient
+                    st.wait_event(j[9])
+            k.bwd_weight_group([(dy, M, N, dy.stride(0), x, K, x.stride(0), dw, db, int(made_ev is not None))
+                                for dy, M, N, x, K, dw, db, _key, _st, made_ev in part])
         waiters = [cur]
         if everyone_waits:
             waiters += [s_ for s_ in _SIDE_STREAM_OBJS if s_.cuda_stream != cur.cuda_stream]
@@ -720,7 +716,6 @@ def _note_made(key, dw, db):
 def _bwd_weight(dy, x, rows, K, want_db=True, key=None):
     """dw [N x K] = dy^T x(rows), db [N]; dy may be the combined [M x 2N] buffer [dh | dg].  `key`: identity of the weight
     (its data pointer) for the deferred form above."""
-    lib = _lib.load()
     M, N = dy.shape
     dw = torch.empty((N, K), device=dy.device)
     db = torch.empty(N, device=dy.device) if want_db else None
@@ -730,43 +725,47 @@ def _bwd_weight(dy, x, rows, K, want_db=True, key=None):
             return d
     elif key is not None and _DEFER[0] is not None:
         _DEFER[0]["uses"][key] = _DEFER[0]["uses"].get(key, 0) + 1
-    nb = lib.evae_dense_bwd_weight_workspace_bytes(M, N, K)
-    ws = _workspace("wgrad", nb, dy.device)
-    _lib.check(lib.evae_dense_bwd_weight(_p(dy), M, N, dy.stride(0), _p(x), _p(rows), K, x.stride(0), _p(dw),
-                                         _p(db), 0, _p(ws), ws.numel(), _stream()), "evae_dense_bwd_weight")
+    launch.Launcher(dy.device).bwd_weight_call(dy, M, N, dy.stride(0), x, rows, K, x.stride(0), dw, db)()
     return _note_made(key, dw, db)
 
 
 def _bwd_data(dy1_ptr, w1, dy2_ptr, w2, M, N, ldy, device, out_prev=None, s_prev=None, out=None, dg_ptr=None, ldo=None):
-    """dx [M x K] = dy1 W1 (+ dy2 W2); with out_prev/s_prev (forward output and gate of the layer below) the gate derivative of the layer below is applied
-    in the epilogue and (dh, dg) are written instead (optionally into the halves of one [M x 2K] buffer)."""
-    lib = _lib.load()
+    """Launcher.bwd_data_call on the current stream (operands as tensors or addresses); without `out`, dx [M x K] is allocated
+    here.  With out_prev / s_prev, (dh, dg) of the layer below may go into the halves of one [M x 2K] buffer (out, dg_ptr, ldo)."""
     K = w1.shape[1]
     if out is None:
         out = torch.empty((M, K), device=device)
         ldo = K
-    np_ = 2 if dy2_ptr is not None else 1
-    nb = lib.evae_dense_bwd_data_workspace_bytes(M, N, K, np_)
-    ws = _workspace("dgrad", nb, device)
-    out_ptr = out if isinstance(out, int) else out.data_ptr()
-    _lib.check(lib.evae_dense_bwd_data(_vp(dy1_ptr), _p(w1), None if dy2_ptr is None else _vp(dy2_ptr), _p(w2),
-                                       M, N, ldy, K, _p(out_prev), _p(s_prev), _vp(out_ptr),
-                                       None if dg_ptr is None else _vp(dg_ptr), ldo, _p(ws), ws.numel(), _stream()),
-               "evae_dense_bwd_data")
+    launch.Launcher(device).bwd_data_call(dy1_ptr, w1, dy2_ptr, w2, M, N, ldy, K, out_prev, s_prev, out, dg_ptr, ldo)()
     return out
 
 
-def _gated_bwd(dout, gout, s, wh, wg, dpre):
-    """A gated layer's backward wrt its input (reference utils/nn.py:62-68 under autograd): fills dpre = [dh | dg] for the weight
-    gradient and returns dx = dh Wh + dg Wg (evae_gated_dense_bwd: one launch for batch-sized row counts)."""
-    lib = _lib.load()
+def _dout_rows(dout, N):
+    """a gated layer's upstream gradient as the kernels read it: fp32 rows of unit stride (a column block of a wider gradient --
+    half of a torch.cat's -- is read where it lies)"""
+    if dout.dtype == torch.float32 and dout.dim() == 2 and dout.stride(1) == 1 and dout.stride(0) >= N:
+        return dout
+    return _f32(dout)
+
+
+def _gated_bwd(dout, gout, s, wh, wg):
+    """A gated layer's backward wrt its input (reference utils/nn.py:62-68 under autograd): (dpre = [dh | dg] for the weight
+    gradient, dx = dh Wh + dg Wg) -- Launcher.gated_bwd."""
     M, N = gout.shape
     K = wh.shape[1]
+    dpre = torch.empty((M, 2 * N), device=gout.device)
     dx = torch.empty((M, K), device=gout.device)
-    ws = _workspace("dgrad", lib.evae_dense_bwd_data_workspace_bytes(M, N, K, 2), gout.device)
-    _lib.check(lib.evae_gated_dense_bwd(_p(dout), dout.stride(0), _p(gout), _p(s), M, N, _p(wh), _p(wg), K, _p(dpre), 2 * N,
-                                        _p(dx), K, _p(ws), ws.numel(), _stream()), "evae_gated_dense_bwd")
-    return dx
+    launch.Launcher(gout.device).gated_bwd(dout, dout.stride(0), gout, s, M, N, wh, wg, K, dpre, dx)
+    return dpre, dx
+
+
+def _gate_bwd(dout, gout, s):
+    """The gate derivative alone: dpre = [dh | dg], one buffer for one weight-gradient GEMM."""
+    M, N = gout.shape
+    dpre = torch.empty((M, 2 * N), device=gout.device)
+    _lib.check(_lib.load().evae_gated_dense_bwd_input_ld(_p(dout), dout.stride(0), _p(gout), _p(s), M, N, _p(dpre), _p(dpre.data_ptr() + 4 * N),
+                                                         2 * N, _stream()), "evae_gated_dense_bwd_input_ld")
+    return dpre
 
 
 def _rows_x(x, rows):
@@ -821,7 +820,6 @@ class GatedDenseFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, rows, wh, bh, wg, bg):
-        lib = _lib.load()
         _need_cuda(x, rows, wh, wg)
         x, rows, M = _rows_x(x, rows)
         wh, wg = _f32(wh), _f32(wg)
@@ -829,13 +827,7 @@ class GatedDenseFn(torch.autograd.Function):
         out = torch.empty((M, N), device=x.device)
         need_grad = any(ctx.needs_input_grad)
         s = torch.empty_like(out) if need_grad else None     # the backward needs out and s only (dg = dout*out*(1-s))
-        nb = lib.evae_dense_fwd_workspace_bytes(M, K, N, 1)
-        ws = _workspace("fwd", nb, x.device)
-        ex_, pipe_ = gemm_pipe(M, N, True, 2.0 * M * K * 2 * N) if rows is None else (None, "fp32-mfma")
-        probed("gated_dense_fwd M=%d K=%d N=%d%s" % (M, K, N, " (row gather)" if rows is not None else ""), 2.0 * M * K * 2 * N,
-               lambda: _lib.check(lib.evae_gated_dense_fwd(_p(x), _p(rows), M, K, x.stride(0), _p(wh), _p(bh), _p(wg), _p(bg),
-                                                           N, _p(out), None, _p(s), _p(ws), ws.numel(), _stream()),
-                                  "evae_gated_dense_fwd"), executed=ex_, pipe=pipe_)
+        launch.Launcher(x.device).gated_fwd(x, rows, M, K, x.stride(0), wh, bh, wg, bg, N, out, None, s)
         if need_grad:
             ctx.save_for_backward(x, rows, wh, wg, out, s)
         ctx.has_bias = (bh is not None, bg is not None)
@@ -843,22 +835,16 @@ class GatedDenseFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        lib = _lib.load()
         x, rows, wh, wg, gout, s = ctx.saved_tensors
-        M, N = gout.shape
-        if not (dout.dtype == torch.float32 and dout.dim() == 2 and dout.stride(1) == 1 and dout.stride(0) >= N):
-            dout = _f32(dout)           # (a column block of a wider gradient -- half of a torch.cat's -- is read where it lies)
-        K = wh.shape[1]
-        dpre = torch.empty((M, 2 * N), device=gout.device)          # [dh | dg]: one buffer, one weight-grad GEMM
-        base = dpre.data_ptr()
+        N, K = wh.shape
+        dout = _dout_rows(dout, N)
         dx = None
         if ctx.needs_input_grad[0]:
             if rows is not None:
                 raise _lib.EvaeError("gradient wrt a row-gathered input is not supported")
-            dx = _gated_bwd(dout, gout, s, wh, wg, dpre)           # gate derivative + data gradient (one launch when batch-sized)
+            dpre, dx = _gated_bwd(dout, gout, s, wh, wg)           # gate derivative + data gradient (one launch when batch-sized)
         else:
-            _lib.check(lib.evae_gated_dense_bwd_input_ld(_p(dout), dout.stride(0), _p(gout), _p(s), M, N, _vp(base), _vp(base + 4 * N),
-                                                         2 * N, _stream()), "evae_gated_dense_bwd_input_ld")
+            dpre = _gate_bwd(dout, gout, s)
         dw, db = _bwd_weight(dpre, x, rows, K, key=wh.data_ptr())  # [dWh ; dWg], [dbh ; dbg]
         if dw is None:             # added, behind the backward pass, to the gradient the layer's other application made (_try_defer)
             return (dx, None, None, None, None, None)
@@ -871,15 +857,12 @@ class GatedDenseDataFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, wh, bh, wg, bg):
-        lib = _lib.load()
         _need_cuda(x, wh, wg)
         x, _, M = _rows_x(x, None)
         wh, wg = _f32(wh), _f32(wg)
         N, K = wh.shape
         out = torch.empty((M, N), device=x.device); s = torch.empty_like(out)
-        ws = _workspace("fwd", lib.evae_dense_fwd_workspace_bytes(M, K, N, 1), x.device)
-        _lib.check(lib.evae_gated_dense_fwd(_p(x), None, M, K, x.stride(0), _p(wh), _p(bh), _p(wg), _p(bg), N, _p(out), None, _p(s),
-                                            _p(ws), ws.numel(), _stream()), "evae_gated_dense_fwd")
+        launch.Launcher(x.device).gated_fwd_call(x, None, M, K, x.stride(0), wh, bh, wg, bg, N, out, None, s)()
         ctx.save_for_backward(wh, wg, out, s)
         ctx.mark_non_differentiable(s)
         ctx.set_materialize_grads(False)
@@ -887,15 +870,11 @@ class GatedDenseDataFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout, _ds):
-        lib = _lib.load()
         wh, wg, gout, s = ctx.saved_tensors
         if dout is None or not ctx.needs_input_grad[0]:
             return None, None, None, None, None
-        M, N = gout.shape
-        if not (dout.dtype == torch.float32 and dout.dim() == 2 and dout.stride(1) == 1 and dout.stride(0) >= N):
-            dout = _f32(dout)
-        dpre = torch.empty((M, 2 * N), device=gout.device)
-        return _gated_bwd(dout, gout, s, wh, wg, dpre), None, None, None, None
+        _dpre, dx = _gated_bwd(_dout_rows(dout, gout.shape[1]), gout, s, wh, wg)
+        return dx, None, None, None, None
 
 
 class GatedDenseParamFn(torch.autograd.Function):
@@ -913,20 +892,15 @@ class GatedDenseParamFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        lib = _lib.load()
         if dout is None:
             return (None,) * 7
         gout, s, x = ctx.saved_tensors
-        M, N = gout.shape
-        if not (dout.dtype == torch.float32 and dout.dim() == 2 and dout.stride(1) == 1 and dout.stride(0) >= N):
-            dout = _f32(dout)
+        N = gout.shape[1]
+        dout = _dout_rows(dout, N)
         st = torch.cuda.current_stream()
         for t in (gout, s, x, dout):       # made on another stream's pool, read here
             t.record_stream(st)
-        dpre = torch.empty((M, 2 * N), device=gout.device)
-        base = dpre.data_ptr()
-        _lib.check(lib.evae_gated_dense_bwd_input_ld(_p(dout), dout.stride(0), _p(gout), _p(s), M, N, _vp(base), _vp(base + 4 * N),
-                                                     2 * N, _stream()), "evae_gated_dense_bwd_input_ld")
+        dpre = _gate_bwd(dout, gout, s)
         dw, db = _bwd_weight(dpre, x, None, ctx.K)
         return (None, None, None, dw[:N], (db[:N] if ctx.has_bias[0] else None), dw[N:], (db[N:] if ctx.has_bias[1] else None))
 
@@ -1002,7 +976,6 @@ class LinearFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, rows, w, b, act, lo, hi):
-        lib = _lib.load()
         _need_cuda(x, rows, w)
         x, rows, M = _rows_x(x, rows)
         w = _f32(w)
@@ -1010,10 +983,7 @@ class LinearFn(torch.autograd.Function):
         y = torch.empty((M, N), device=x.device)
         need_grad = any(ctx.needs_input_grad)
         pre = torch.empty_like(y) if (need_grad and act == ACT_HARDTANH) else None
-        nb = lib.evae_dense_fwd_workspace_bytes(M, K, N, 0)
-        ws = _workspace("fwd", nb, x.device)
-        _lib.check(lib.evae_linear_fwd(_p(x), _p(rows), M, K, x.stride(0), _p(w), _p(b), N, act, float(lo),
-                                       float(hi), _p(y), _p(pre), _p(ws), ws.numel(), _stream()), "evae_linear_fwd")
+        launch.Launcher(x.device).linear_fwd(x, M, K, x.stride(0), w, b, N, act, float(lo), float(hi), y, pre, rows=rows)
         if need_grad:
             ctx.save_for_backward(x, rows, w, pre if pre is not None else y)
         ctx.act = (act, float(lo), float(hi))
@@ -1189,90 +1159,75 @@ class Conv2dFn(torch.autograd.Function):
         # or when the weight gradient qualifies anyway (then x is re-laid out once)
         cl_w = bool(lib.evae_conv2d_cl_supported(C.byref(d), 2, int(gated))) and cl
         cl_d = bool(lib.evae_conv2d_cl_supported(C.byref(d), 1, int(gated))) and cl
-        if cl:
-            dout = _cl(dout.float())
-        else:
-            dout = _f32(dout)
+        if gated and act != ACT_NONE:
+            raise _lib.EvaeError("gated conv with an activation on h: compose it from two plain convs")
+        need_dx = ctx.needs_input_grad[0]
+        dout = _cl(dout.float()) if cl else _f32(dout)
         n = dout.numel()
+
+        def act_bwd(dst):
+            _lib.check(lib.evae_act_bwd(_p(dout), _p(aux), n, act, lo, hi, _p(dst), _stream()), "evae_act_bwd")
+
+        # 1. the gradient at the convolution's output(s), once: dy (channels-last family) or dh, dg (NCHW family)
+        dh = dg = dy = None
         if cl:
             # [dh | dg | zero padding] per pixel in ONE buffer: logical [N, ldy, OH, OW], channels-last
             ldy = lib.evae_conv2d_cl_dy_stride(ctot)
-            if ldy == ctot:
-                dy = torch.empty((d.N, ldy, OH, OW), device=dev, memory_format=CL)
-            else:
-                dy = torch.empty((d.N, ldy, OH, OW), device=dev, memory_format=CL).zero_()
+            dy = torch.empty((d.N, ldy, OH, OW), device=dev, memory_format=CL)
+            if ldy != ctot:
+                dy.zero_()
             if gated:
-                if act != ACT_NONE:
-                    raise _lib.EvaeError("gated conv with an activation on h: compose it from two plain convs")
                 # rows = pixels, columns = Co channels: dh to columns [0, Co), dg to [Co, 2 Co)
-                _lib.check(lib.evae_gated_dense_bwd_input(_p(dout), _p(aux), _p(s), n // d.Co, d.Co, _p(dy),
-                                                          C.c_void_p(dy.data_ptr() + 4 * d.Co), ldy, _stream()),
-                           "evae_gated_dense_bwd_input")
-            elif ldy == ctot and act != ACT_NONE:
-                _lib.check(lib.evae_act_bwd(_p(dout), _p(aux), n, act, lo, hi, _p(dy), _stream()), "evae_act_bwd")
-            elif ldy == ctot:
-                dy = dout
-            else:
+                _lib.check(lib.evae_gated_dense_bwd_input(_p(dout), _p(aux), _p(s), n // d.Co, d.Co, _p(dy), _p(dy.data_ptr() + 4 * d.Co),
+                                                          ldy, _stream()), "evae_gated_dense_bwd_input")
+            elif ldy != ctot:
                 src = dout
                 if act != ACT_NONE:
                     src = torch.empty_like(dout)
-                    _lib.check(lib.evae_act_bwd(_p(dout), _p(aux), n, act, lo, hi, _p(src), _stream()), "evae_act_bwd")
+                    act_bwd(src)
                 dy[:, :ctot].copy_(src)
-            dw = torch.empty((ctot, K), device=dev); db = torch.empty(ctot, device=dev)
-            if cl_w:
-                nb = lib.evae_conv2d_cl_workspace_bytes(C.byref(d), 2, int(gated))
-                ws = _workspace("conv", nb, dev)
-                _lib.check(lib.evae_conv2d_cl_bwd_weight(_p(dy), _p(x), C.byref(d), int(gated), _p(dw), _p(db), _p(ws),
-                                                         ws.numel(), _stream()), "evae_conv2d_cl_bwd_weight")
-            dx = None
-            if ctx.needs_input_grad[0] and cl_d:
-                dx = torch.empty(x.shape, device=dev, memory_format=CL)
-                nb = lib.evae_conv2d_cl_workspace_bytes(C.byref(d), 1, int(gated))
-                ws = _workspace("conv", nb, dev)
-                _lib.check(lib.evae_conv2d_cl_bwd_data(_p(dy), _p(wh), _p(wg), C.byref(d), _p(dx), _p(ws), ws.numel(),
-                                                       _stream()), "evae_conv2d_cl_bwd_data")
-            if (not cl_w) or (ctx.needs_input_grad[0] and not cl_d):
-                # the rest through the NCHW kernels (e.g. the data gradient of a 6-channel output layer)
-                dhn = dy[:, :d.Co].contiguous()
-                dgn = dy[:, d.Co:ctot].contiguous() if gated else None
+            elif act != ACT_NONE:
+                act_bwd(dy)
+            else:
+                dy = dout
+            if (not cl_w) or (need_dx and not cl_d):
+                # what the channels-last kernels do not take goes through the NCHW ones (e.g. the data gradient of a thin first layer)
+                dh = dy[:, :d.Co].contiguous()
+                dg = dy[:, d.Co:ctot].contiguous() if gated else None
                 xn = x.contiguous()
-                if not cl_w:
-                    nb = lib.evae_conv2d_workspace_bytes(C.byref(d), 2, int(gated))
-                    ws = _workspace("conv", nb, dev)
-                    _lib.check(lib.evae_conv2d_bwd_weight(_p(dhn), _p(dgn), _p(xn), C.byref(d), _p(dw), _p(db), _p(ws),
-                                                          ws.numel(), _stream()), "evae_conv2d_bwd_weight")
-                if ctx.needs_input_grad[0] and not cl_d:
-                    dx = torch.empty(xn.shape, device=dev)
-                    nb = lib.evae_conv2d_workspace_bytes(C.byref(d), 1, int(gated))
-                    ws = _workspace("conv", nb, dev)
-                    _lib.check(lib.evae_conv2d_bwd_data(_p(dhn), _p(wh), _p(dgn), _p(wg), C.byref(d), _p(dx), _p(ws),
-                                                        ws.numel(), _stream()), "evae_conv2d_bwd_data")
         else:
+            xn = x
             if gated:
-                if act != ACT_NONE:
-                    raise _lib.EvaeError("gated conv with an activation on h: compose it from two plain convs")
                 dh = torch.empty_like(dout); dg = torch.empty_like(dout)
                 _lib.check(lib.evae_gated_dense_bwd_input(_p(dout), _p(aux), _p(s), 1, n, _p(dh), _p(dg), n, _stream()),
                            "evae_gated_dense_bwd_input")
+            elif act != ACT_NONE:
+                dh = torch.empty_like(dout)
+                act_bwd(dh)
             else:
-                dg = None
-                if act != ACT_NONE:
-                    dh = torch.empty_like(dout)
-                    _lib.check(lib.evae_act_bwd(_p(dout), _p(aux), n, act, lo, hi, _p(dh), _stream()), "evae_act_bwd")
-                else:
-                    dh = dout
-            dw = torch.empty((ctot, K), device=dev); db = torch.empty(ctot, device=dev)
-            nb = lib.evae_conv2d_workspace_bytes(C.byref(d), 2, int(gated))
-            ws = _workspace("conv", nb, dev)
-            _lib.check(lib.evae_conv2d_bwd_weight(_p(dh), _p(dg), _p(x), C.byref(d), _p(dw), _p(db), _p(ws), ws.numel(),
-                                                  _stream()), "evae_conv2d_bwd_weight")
-            dx = None
-            if ctx.needs_input_grad[0]:
-                dx = torch.empty_like(x)
-                nb = lib.evae_conv2d_workspace_bytes(C.byref(d), 1, int(gated))
-                ws = _workspace("conv", nb, dev)
-                _lib.check(lib.evae_conv2d_bwd_data(_p(dh), _p(wh), _p(dg), _p(wg), C.byref(d), _p(dx), _p(ws), ws.numel(),
-                                                    _stream()), "evae_conv2d_bwd_data")
+                dh = dout
+        # 2. the weight gradient, on the family cl_w picks
+        dw = torch.empty((ctot, K), device=dev); db = torch.empty(ctot, device=dev)
+        if cl_w:
+            ws = _workspace("conv", lib.evae_conv2d_cl_workspace_bytes(C.byref(d), 2, int(gated)), dev)
+            _lib.check(lib.evae_conv2d_cl_bwd_weight(_p(dy), _p(x), C.byref(d), int(gated), _p(dw), _p(db), _p(ws), ws.numel(), _stream()),
+                       "evae_conv2d_cl_bwd_weight")
+        else:
+            ws = _workspace("conv", lib.evae_conv2d_workspace_bytes(C.byref(d), 2, int(gated)), dev)
+            _lib.check(lib.evae_conv2d_bwd_weight(_p(dh), _p(dg), _p(xn), C.byref(d), _p(dw), _p(db), _p(ws), ws.numel(), _stream()),
+                       "evae_conv2d_bwd_weight")
+        # 3. the data gradient, on the family cl_d picks
+        dx = None
+        if need_dx and cl_d:
+            dx = torch.empty(x.shape, device=dev, memory_format=CL)
+            ws = _workspace("conv", lib.evae_conv2d_cl_workspace_bytes(C.byref(d), 1, int(gated)), dev)
+            _lib.check(lib.evae_conv2d_cl_bwd_data(_p(dy), _p(wh), _p(wg), C.byref(d), _p(dx), _p(ws), ws.numel(), _stream()),
+                       "evae_conv2d_cl_bwd_data")
+        elif need_dx:
+            dx = torch.empty(xn.shape, device=dev)
+            ws = _workspace("conv", lib.evae_conv2d_workspace_bytes(C.byref(d), 1, int(gated)), dev)
+            _lib.check(lib.evae_conv2d_bwd_data(_p(dh), _p(wh), _p(dg), _p(wg), C.byref(d), _p(dx), _p(ws), ws.numel(), _stream()),
+                       "evae_conv2d_bwd_data")
         gwh = dw[:d.Co].reshape(shp)
         gwg = dw[d.Co:].reshape(shp) if gated else None
         return (dx, gwh, db[:d.Co] if has_bh else None, gwg, (db[d.Co:] if (gated and has_bg) else None),
@@ -1394,6 +1349,18 @@ def conv_stack_depth(x_shape, layers):
     return 0
 
 
+def _pad_last_layer(layer, padc, biases):
+    """(wh, bh, wg, bg) of the last layer the image pipeline takes, with padc zero output channels behind the real ones: the layer
+    runs at a multiple of 32 output channels (conv_stack_depth).  biases: pad them too (the forward pass; the backward pass reads
+    the filters only)."""
+    wh, bh, wg, bg = layer
+    zw = wh.new_zeros((padc,) + tuple(wh.shape[1:]))
+
+    def bias(t):
+        return t if (t is None or not biases) else torch.cat((t.float(), t.new_zeros(padc)))
+    return [torch.cat((_f32(wh), zw)), bias(bh), torch.cat((_f32(wg), zw)), bias(bg)]
+
+
 class GatedConvStackFn(torch.autograd.Function):
     """Layers 0 .. b - 1 of a stack of gated convolutions act(h(x)) * sigmoid(g(x)) (reference utils/nn.py:72-97, as
     models/convHVAE_2level.py:21-46 chains them) with every activation between two layers as a pre-split pixel image
@@ -1411,12 +1378,7 @@ class GatedConvStackFn(torch.autograd.Function):
         _need_cuda(x, *[t for t in params if t is not None])
         co_real = [int(L[i][0].shape[0]) for i in range(b)]
         if b >= 2 and co_real[b - 1] % 32:
-            # last layer of the module: output channels zero-padded to a multiple of 32 (conv_stack_depth)
-            padc = _pad32(co_real[b - 1]) - co_real[b - 1]
-            wh_, bh_, wg_, bg_ = L[b - 1]
-            zw = wh_.new_zeros((padc,) + tuple(wh_.shape[1:]))
-            L[b - 1] = [torch.cat((_f32(wh_), zw)), None if bh_ is None else torch.cat((bh_.float(), bh_.new_zeros(padc))),
-                        torch.cat((_f32(wg_), zw)), None if bg_ is None else torch.cat((bg_.float(), bg_.new_zeros(padc)))]
+            L[b - 1] = _pad_last_layer(L[b - 1], _pad32(co_real[b - 1]) - co_real[b - 1], biases=True)
         x = _cl(x.float())
         dev = x.device
         need_grad = any(ctx.needs_input_grad[2:])
@@ -1492,10 +1454,7 @@ class GatedConvStackFn(torch.autograd.Function):
             full = torch.empty((N, shp[b - 1][0], dout.shape[2], dout.shape[3]), device=dev, memory_format=CL).zero_()
             full[:, :co_real[b - 1]] = dout
             dout = full
-            wlast = L[b - 1]
-            padc = shp[b - 1][0] - co_real[b - 1]
-            zw = wlast[0].new_zeros((padc,) + tuple(wlast[0].shape[1:]))
-            L[b - 1] = [torch.cat((_f32(wlast[0]), zw)), wlast[1], torch.cat((_f32(wlast[2]), zw)), wlast[3]]
+            L[b - 1] = _pad_last_layer(L[b - 1], shp[b - 1][0] - co_real[b - 1], biases=False)    # (the data gradient reads the filters only)
         dout = _cl(dout.float())
         grads = [None] * (4 * b)
 
@@ -1543,8 +1502,6 @@ class GatedConvStackFn(torch.autograd.Function):
             _lib.check(lib.evae_cw_bwd_data_gate(_p(dyimg), int(planar[i]), C.byref(d), _p(_f32(L[i][0])), _p(_f32(L[i][2])), _p(imgs[i - 1]),
                                                  _p(gates[i - 1]), _p(nimg), _p(nf), _p(ws), ws.numel(), _stream()), "evae_cw_bwd_data_gate")
             imgs[i - 1] = None; gates[i - 1] = None
-            if i - 1 < len(outf):
-                pass
             dyimg, dyf = nimg, nf
         # layer 0: weight gradient on the channels-last kernels from the merged fp32 gradient
         d0 = ds[0]
@@ -1790,13 +1747,13 @@ class ResStackFn(torch.autograd.Function):
         _lib.check(lib.evae_cw_res_run_fwd(C.byref(d), nb, _p(filt[0]), bias, _p(imgs[0]), _p(x), outf, oimg, st), "evae_cw_res_run_fwd")
         if need_grad:
             ctx.save_for_backward(*ws_)
-            ctx.keep = (imgs, d, [b is not None for b in bs_], filt[1], bs_)
+            ctx.keep = (imgs, d, [b is not None for b in bs_], filt[1])
         return y_last.permute(0, 3, 1, 2)
 
     @staticmethod
     def backward(ctx, dout):
         lib = _lib.load()
-        imgs, d, has_b, bimg, bs_ = ctx.keep
+        imgs, d, has_b, bimg = ctx.keep
         ctx.keep = None
         ws_ = list(ctx.saved_tensors)
         nb = len(ws_)
@@ -1821,10 +1778,9 @@ class ResStackFn(torch.autograd.Function):
         aim = VP(*[imgs[k].data_ptr() for k in range(nb)])
         dxf = VP(*[dxs[k].data_ptr() for k in range(nb)])
         dxi = VP(*[dimgs[k].data_ptr() if k >= 1 else None for k in range(nb)])
-        dimg_top = dtop
         dwp = VP(*[dws[k].data_ptr() for k in range(nb)])
         dbp = VP(*[dbs[k].data_ptr() for k in range(nb)])
-        _lib.check(lib.evae_cw_res_run_bwd(C.byref(d), nb, _p(bimg), aim, _p(dimg_top), _p(dy), dxf, dxi, dwp, dbp, _p(ws), ws.numel(), st),
+        _lib.check(lib.evae_cw_res_run_bwd(C.byref(d), nb, _p(bimg), aim, _p(dtop), _p(dy), dxf, dxi, dwp, dbp, _p(ws), ws.numel(), st),
                    "evae_cw_res_run_bwd")
         grads = []
         for k in range(nb):
@@ -1998,10 +1954,9 @@ def heads_reparam(h, wm, bm, wl, bl, eps, lo, hi):
 
 def _heads_bwd(h, wm, wl, dmu, dlvp, want_dh, has_bias):
     """what the two heads' backward shares: dh over both heads in one data gradient, both weight gradients in one grouped launch"""
-    lib = _lib.load()
     M, K = h.shape
     Z = wm.shape[0]
-    dh = _bwd_data(dmu.data_ptr(), wm, dlvp.data_ptr(), wl, M, Z, Z, h.device) if want_dh else None
+    dh = _bwd_data(dmu, wm, dlvp, wl, M, Z, Z, h.device) if want_dh else None
     if M <= 128 and Z % 4 == 0 and K % 4 == 0 and h.stride(0) % 4 == 0:
         # each head on its own: deferred behind the backward pass when its weight allows (ops.deferred_wgrads; the mean head of
         # q(z2 | x) also encodes the exemplar rows and does not), what is left as one grouped launch here
@@ -2012,13 +1967,9 @@ def _heads_bwd(h, wm, wl, dmu, dlvp, want_dh, has_bias):
                 res[name] = d
             else:
                 dw_ = torch.empty((Z, K), device=h.device); db_ = torch.empty(Z, device=h.device)
-                res[name] = (dw_, db_); now.append((dy_, dw_, db_))
+                res[name] = (dw_, db_); now.append((dy_, M, Z, dy_.stride(0), h, K, h.stride(0), dw_, db_))
         if now:
-            arr = (_lib.WgradJob * len(now))()
-            for j, (dy_, dw_, db_) in enumerate(now):
-                arr[j].dy = dy_.data_ptr(); arr[j].x = h.data_ptr(); arr[j].dw = dw_.data_ptr(); arr[j].db = db_.data_ptr()
-                arr[j].M, arr[j].N, arr[j].K, arr[j].ldy, arr[j].ldx = M, Z, K, dy_.stride(0), h.stride(0)
-            _lib.check(lib.evae_dense_bwd_weight_group(C.cast(arr, C.c_void_p), len(now), _stream()), "evae_dense_bwd_weight_group")
+            launch.Launcher(h.device).bwd_weight_group(now)
         (dwm, dbm), (dwl, dbl) = res["m"], res["l"]
     else:
         dwm, dbm = _bwd_weight(dmu, h, None, K)

@@ -12,7 +12,8 @@ Streams and events are ordinals in order of first appearance, so two recordings 
 whatever the addresses were.  A captured step replays without Python: equal recordings of its capture are the same graph.
 
 The golden tests/golden/g28_fused_step_traces.json holds the recordings of CASES on the commit named inside it; nothing here
-rewrites it (python tests/step_trace.py OUT.json COMMIT is how it was made there).  Every case is recorded on its second run behind a
+rewrites it (python tests/step_trace.py OUT.json COMMIT is how it was made there); tests/golden/g29_modular_step_traces.json holds
+those of MODULAR_CASES, what the autograd Functions of evae/ops.py issue (... OUT.json COMMIT modular).  Every case is recorded on its second run behind a
 fresh set of named workspaces (record() below): the first run leaves the workspaces, the one-element constants and the
 zero-filled image buffers as an earlier step of the same shape leaves them, so a recording does not depend on what ran before."""
 import contextlib
@@ -156,7 +157,7 @@ def _exemplar_model(C_, seed, batch=B, **kw):
     import golden_inputs as gi
     import smoke_case
     args = smoke_case.vae_args(number_components=C_, training_set_size=N, batch_size=batch, **kw)
-    if args.prior == "exemplar_prior":
+    if args.prior == "exemplar_prior" and args.model_name == "vae":
         model, _ = smoke_case.build_model(torch, np, orc, args)
     else:
         from utils.utils import importing_model
@@ -272,6 +273,131 @@ CASES = {
 }
 
 
+# ------------------------------------------------------------------------------------------------ the modular operators' cases
+def _hvae2(t):
+    """one eager training step of hvae_2level on evae.ops' autograd Functions, as utils/training.py issues it"""
+    from evae import ops
+    args, model, data, dataset = _exemplar_model(200, 36, model_name="hvae_2level")
+    xb = torch.from_numpy(data[:B]).cuda()
+    ib = torch.arange(B).reshape(-1, 1).cuda()
+    torch.manual_seed(37); torch.cuda.manual_seed(37)       # (the exemplar draws decide how many distinct rows are encoded)
+    torch.cuda.synchronize()
+    with t:
+        t.mark("forward")
+        loss, RE, KL = model.calculate_loss((xb, ib), 0.5, average=False, dataset=dataset)
+        t.mark("backward")
+        with ops.deferred_wgrads(loss):
+            loss.sum().backward()
+            t.mark("deferred")
+    torch.cuda.synchronize()
+
+
+def _hvae2_leaf(t):
+    """(models/AbsHModel.py reads EVAE_HVAE_LEAF_STREAM once, at import: the case sets what that read leaves behind as well)"""
+    import models.AbsHModel as hm
+    old, hm._LEAF_STREAM = hm._LEAF_STREAM, True
+    try:
+        with _env(EVAE_HVAE_LEAF_STREAM="1"):
+            _hvae2(t)
+    finally:
+        hm._LEAF_STREAM = old
+
+
+# (N, C, H, W, Co, k, stride, pad), gated?, Hardtanh on the plain layer?, x.requires_grad?  Which family a geometry runs on is the
+# library's answer (evae_conv2d_cl_supported): the first four rows -- rows of tests/test_gpu_conv.py's tables -- all run on the
+# channels-last kernels, weight AND data gradient; the rows behind them take the other branches of Conv2dFn.backward
+CONV_LAYERS = (((5, 1, 28, 28, 32, 3, 1, 1), True, False, False),           # a thin first layer: patch matrix + dense GEMM
+               ((5, 32, 28, 28, 32, 3, 2, 1), True, False, False),
+               ((5, 32, 28, 28, 32, 3, 2, 1), False, True, False),          # the activation's derivative written into dy
+               ((7, 64, 7, 7, 6, 3, 1, 1), True, False, True),              # with the data gradient
+               ((5, 32, 28, 28, 32, 3, 2, 1), False, False, False),         # plain, no activation: dy is the upstream gradient itself
+               # 8 channels and 72 taps: neither a patch matrix nor the channels-last GEMM -- the NCHW family (the layers of
+               # test_conv2d_activations_and_modules)
+               ((4, 8, 10, 10, 6, 3, 2, 1), True, False, False),
+               ((4, 8, 10, 10, 5, 3, 1, 1), False, True, False),
+               # channels-last forward, 10 / 5 gradient channels per pixel (zero-padded to 32 in dy): both gradients on the NCHW kernels
+               ((2, 1, 9, 11, 5, 3, 2, 1), True, False, True),
+               ((2, 1, 9, 11, 5, 3, 2, 1), False, True, False))
+
+
+def _conv_layers(t):
+    from evae import ops
+    rs = np.random.RandomState(38)
+    jobs = []
+    for (n, c, h, w, co, k, s, p), gated, clamp, x_grad in CONV_LAYERS:
+        x = torch.from_numpy(rs.standard_normal((n, c, h, w)).astype(np.float32)).cuda().requires_grad_(x_grad)
+        prm = [torch.from_numpy((rs.standard_normal(shape) * 0.1).astype(np.float32)).cuda().requires_grad_(True)
+               for shape in ((co, c, k, k), (co,), (co, c, k, k), (co,))]
+        gout = torch.from_numpy(rs.standard_normal((n, co, (h + 2 * p - k) // s + 1, (w + 2 * p - k) // s + 1)).astype(np.float32)).cuda()
+        jobs.append((x, prm, gout, s, p, gated, clamp))
+    torch.cuda.synchronize()
+    with t:
+        for i, (x, (wh, bh, wg, bg), gout, s, p, gated, clamp) in enumerate(jobs):
+            t.mark("layer %d forward" % i)
+            if gated:
+                y = ops.gated_conv2d(x, wh, bh, wg, bg, s, p)
+            else:
+                y = ops.conv2d(x, wh, bh, s, p, *((ops.ACT_HARDTANH, -4.5, 0.0) if clamp else ()))
+            t.mark("layer %d backward" % i)
+            y.backward(gout)
+    torch.cuda.synchronize()
+
+
+@contextlib.contextmanager
+def _ops_attr(name, value):
+    from evae import ops
+    old = getattr(ops, name)
+    setattr(ops, name, value)
+    try:
+        yield
+    finally:
+        setattr(ops, name, old)
+
+
+def _conv_stack(t):
+    import test_gpu_conv as tc
+    n = 37
+    net = tc._stack(tc._NARROW, 3).cuda()
+    rs = np.random.RandomState(n)
+    x = torch.from_numpy((rs.rand(n, 1, 28, 28) < 0.3).astype(np.float32)).cuda()
+    gout = torch.from_numpy(rs.standard_normal((n, 6, 7, 7)).astype(np.float32)).cuda()
+    torch.cuda.synchronize()
+    with _ops_attr("CONV_STACK_MIN_IMAGES", 1), t:
+        t.mark("forward")
+        y = net(x)
+        t.mark("backward")
+        y.backward(gout)
+    torch.cuda.synchronize()
+
+
+def _res_run(t):
+    from evae import ops
+    n, c, h, nblk = 9, 48, 14, 2
+    rs = np.random.RandomState(n + c + h)
+    x = torch.from_numpy((rs.standard_normal((n, c, h, h)) * 1.5).astype(np.float32)).cuda().requires_grad_(True)
+    blocks = [(torch.from_numpy((rs.standard_normal((c, c, 3, 3)) / np.sqrt(c * 9)).astype(np.float32)).cuda().requires_grad_(True),
+               torch.from_numpy((rs.standard_normal(c) * 0.1).astype(np.float32)).cuda().requires_grad_(True)) for _ in range(nblk)]
+    gout = torch.from_numpy(rs.standard_normal((n, c, h, h)).astype(np.float32)).cuda()
+    torch.cuda.synchronize()
+    with _ops_attr("RES_STACK_MIN_PIXELS", 1), t:
+        t.mark("forward")
+        y = ops.res_stack(x, blocks)
+        t.mark("backward")
+        y.backward(gout)
+    torch.cuda.synchronize()
+
+
+# name -> (run(trace),): what evae.ops' autograd Functions issue, recorded in tests/golden/g29_modular_step_traces.json
+MODULAR_CASES = {
+    "hvae2_u8": (_hvae2,),
+    "hvae2_fp32": (_with_env(_hvae2, EVAE_U8_STORE="0"),),
+    "hvae2_leaf": (_hvae2_leaf,),
+    "conv_layers": (_conv_layers,),
+    "conv_stack": (_conv_stack,),
+    "res_run": (_res_run,),
+}
+
+
 class _Off:
     """the un-recorded first run of a case"""
 
@@ -320,7 +446,7 @@ def record(name):
     from evae import ops
     ops._ws_retired.extend(ops._ws.values())
     ops._ws.clear()
-    run = CASES[name][0]
+    run = (CASES.get(name) or MODULAR_CASES[name])[0]
     with _distinct_streams():
         run(_Off())
         t = StepTrace()
@@ -336,7 +462,7 @@ if __name__ == "__main__":
         sys.path.insert(0, p)
     out = {"commit": subprocess.check_output(["git", "rev-parse", "HEAD"], cwd=root).decode().strip() if len(sys.argv) < 3 else sys.argv[2],
            "cases": {}}
-    for name in CASES:
+    for name in (MODULAR_CASES if sys.argv[3:] == ["modular"] else CASES):       # OUT.json COMMIT modular: the g29 golden
         try:
             out["cases"][name] = record(name)
             print(name, len(out["cases"][name]), "records", flush=True)

@@ -5,7 +5,10 @@ order (tests/step_trace.py).  A captured step replays without Python, so an equa
 
 The one difference allowed: in the standard-prior cases evae_dense_bwd_data may have become evae_dense_bwd_data_wt with a null
 wT -- the same launch (both are dense_bwd_data_core, csrc/evae_dense.hip).  Each case also asserts the entry points that mark
-its branch, so that none passes by quietly taking another one.  Nothing here rewrites the golden."""
+its branch, so that none passes by quietly taking another one.  Nothing here rewrites the golden.
+
+The same holds the autograd Functions of evae/ops.py (the modular paths: hvae_2level steps, convolution layers, the gated
+convolution stack, a residual run) to tests/golden/g29_modular_step_traces.json -- see MODULAR_MARKERS below."""
 import json
 import os
 
@@ -66,6 +69,55 @@ def test_step_issues_what_the_recorded_commit_issued(recorded, case):
                     or (r[0] == "call" and str(r[2][-1]).startswith("s"))], tail
     if step_trace.CASES[case][1]:
         want, got = [_same_launch(r) for r in want], [_same_launch(r) for r in got]
+    first = next((i for i, (a, b) in enumerate(zip(want, got)) if a != b), None)
+    assert first is None, "record %d: recorded %s, issued %s" % (first, want[first], got[first])
+    assert len(got) == len(want), (len(want), len(got))
+
+
+# ---- the autograd Functions of evae/ops.py (tests/golden/g29_modular_step_traces.json, step_trace.MODULAR_CASES): the same
+# comparison, evae_dense_bwd_data against evae_dense_bwd_data_wt with a null wT allowed in every case
+_HVAE2 = ["evae_heads_reparam_fwd", "evae_heads_density_fwd", "evae_dense_bwd_weight_group"]
+MODULAR_MARKERS = {
+    "hvae2_u8": (_HVAE2 + ["evae_gated_dense_fwd_u8"], []),
+    "hvae2_fp32": (_HVAE2, ["evae_gated_dense_fwd_u8"]),
+    "hvae2_leaf": (_HVAE2 + ["evae_gated_dense_fwd_u8"], []),
+    "conv_layers": (["evae_conv2d_fwd", "evae_conv2d_cl_fwd", "evae_conv2d_bwd_weight", "evae_conv2d_cl_bwd_weight", "evae_conv2d_bwd_data",
+                     "evae_conv2d_cl_bwd_data", "evae_act_bwd"], []),
+    "conv_stack": (["evae_cw_gate_bwd_image"], []),
+    "res_run": (["evae_cw_res_run_fwd", "evae_cw_res_run_bwd"], []),
+}
+
+
+@pytest.fixture(scope="module")
+def recorded_modular():
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "g29_modular_step_traces.json")) as f:
+        return json.load(f)
+
+
+def test_the_modular_cases_are_the_recorded_ones(recorded_modular):
+    assert set(recorded_modular["cases"]) == set(step_trace.MODULAR_CASES) == set(MODULAR_MARKERS)
+    assert len(recorded_modular["commit"]) == 40
+
+
+def _launch_streams(records):
+    return {r[2][-1] for r in records if r[0] == "call" and str(r[2][-1]).startswith("s")}
+
+
+@pytest.mark.parametrize("case", sorted(MODULAR_MARKERS))
+def test_modular_operators_issue_what_the_recorded_commit_issued(recorded_modular, case):
+    want = recorded_modular["cases"][case]
+    got = json.loads(json.dumps(step_trace.record(case)))
+    names = {r[1] for r in got if r[0] == "call"}
+    present, absent = MODULAR_MARKERS[case]
+    assert all(m in names for m in present) and not any(m in names for m in absent), sorted(names)
+    if case.startswith("hvae2"):
+        groups = step_trace.calls(got, "evae_dense_bwd_weight_group")
+        # the batch rows' second use of a weight the exemplar rows' GEMM made: added in place (ops._try_defer)
+        assert any(job[5] == 1 for r in groups for job in r[3]), groups
+        # ... and the scope's own grouped launches, behind the backward pass (ops.deferred_wgrads.__exit__)
+        assert step_trace.calls(got[got.index(["mark", "deferred"]):], "evae_dense_bwd_weight_group")
+        assert len(_launch_streams(got)) >= (3 if case == "hvae2_leaf" else 2), _launch_streams(got)
+    want, got = [_same_launch(r) for r in want], [_same_launch(r) for r in got]
     first = next((i for i, (a, b) in enumerate(zip(want, got)) if a != b), None)
     assert first is None, "record %d: recorded %s, issued %s" % (first, want[first], got[first])
     assert len(got) == len(want), (len(want), len(got))
