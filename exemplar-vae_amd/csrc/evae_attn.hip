@@ -34,6 +34,11 @@
 // attention probabilities, e = ((b H + h) L + i) L + j in 64-bit arithmetic; the flat storage index for the element-wise op) takes
 // word e % 4 of quad e / 4; counter (quad_lo, quad_hi, offset_lo, offset_hi), key (seed_lo, seed_hi); keep <=> u01(word) >= p_drop,
 // kept values scaled by 1 / (1 - p_drop).  p_drop = 0 draws nothing and runs the code without a mask.
+// Where (seed, offset) come from is the ONLY difference between the host-argument launches and the *_dev ones: a DropRng is a launch
+// argument; a DropDev names the two device words [seed, step counter] of a captured step's control block (evae/graph.py) plus the
+// ordinal of the mask within the step, and drop_source() turns either into the DropRng the mask code runs on -- one uniform load of
+// the two words at kernel entry, offset = evae_dropout_step_offset(counter, ordinal).  A replayed graph node carries the pointer and
+// the ordinal; the counter it reads is the replay's.
 #include "evae_common.h"
 #include "evae_philox.h"
 
@@ -49,6 +54,39 @@ struct DropRng {
   uint32_t off_lo, off_hi;
   float p, scale;
 };
+
+// where a *_dev launch takes its Philox words from
+struct DropDev {
+  const int64_t* seed_ctr;    // device: [seed, step counter]
+  uint32_t ordinal;
+  float p, scale;
+};
+
+constexpr uint32_t kDropMaxOrdinal = 65536;
+// 2^63 | (counter mod 2^47) << 16 | ordinal: bit 63 keeps a step's masks apart from the host counter's offsets 0, 1, 2, ...
+__host__ __device__ __forceinline__ uint64_t drop_step_offset(uint64_t counter, uint32_t ordinal) {
+  return (1ull << 63) | ((counter & ((1ull << 47) - 1)) << 16) | (uint64_t)ordinal;
+}
+
+__host__ __device__ __forceinline__ DropRng drop_rng_of(uint64_t seed, uint64_t offset, float p, float scale) {
+  DropRng g;
+  g.key = make_uint2((uint32_t)seed, (uint32_t)(seed >> 32));
+  g.off_lo = (uint32_t)offset;
+  g.off_hi = (uint32_t)(offset >> 32);
+  g.p = p;
+  g.scale = scale;
+  return g;
+}
+
+// the DropRng of a kernel with dropout; without dropout nothing is read (seed_ctr may be null)
+template <bool DROP>
+__device__ __forceinline__ DropRng drop_source(const DropRng& g) { return g; }
+template <bool DROP>
+__device__ __forceinline__ DropRng drop_source(const DropDev& d) {
+  if (!DROP) return drop_rng_of(0, 0, d.p, d.scale);
+  const uint64_t seed = (uint64_t)d.seed_ctr[0], counter = (uint64_t)d.seed_ctr[1];      // (the same address in every lane: one scalar load)
+  return drop_rng_of(seed, drop_step_offset(counter, d.ordinal), d.p, d.scale);
+}
 
 __device__ __forceinline__ uint32_t pick_word(const uint4& r, uint32_t w) { return w == 0 ? r.x : (w == 1 ? r.y : (w == 2 ? r.z : r.w)); }
 __device__ __forceinline__ uint4 drop_quad(const DropRng& g, uint64_t quad) {
@@ -84,10 +122,11 @@ __device__ __forceinline__ float4 scale4(const float4& a, float s) { return make
     for (int half_ = 0, i = p_; half_ < 2 && !(half_ == 1 && L - 1 - p_ == p_); ++half_, i = L - 1 - p_)
 
 // float4 index of row i of head h of image b in a [B*L, H*4] matrix: (b L + i) H + h
-template <bool DROP>
+template <bool DROP, class Src>
 __global__ __launch_bounds__(kAttnThreads) void attn_fwd_kernel(const float4* __restrict__ q, const float4* __restrict__ k,
-                                                                const float4* __restrict__ v, int H, int L, DropRng g,
+                                                                const float4* __restrict__ v, int H, int L, Src src,
                                                                 float4* __restrict__ out, float* __restrict__ lse) {
+  const DropRng g = drop_source<DROP>(src);
   extern __shared__ float4 attn_smem[];
   float4* sk = attn_smem;
   float4* sv = attn_smem + L;
@@ -118,13 +157,14 @@ __global__ __launch_bounds__(kAttnThreads) void attn_fwd_kernel(const float4* __
   }
 }
 
-template <bool DROP>
+template <bool DROP, class Src>
 __global__ __launch_bounds__(kAttnThreads) void attn_bwd_dq_kernel(const float4* __restrict__ q, const float4* __restrict__ k,
                                                                    const float4* __restrict__ v, const float4* __restrict__ out,
                                                                    const float* __restrict__ lse, const float4* __restrict__ dout,
-                                                                   int H, int L, DropRng g, float4* __restrict__ dq,
+                                                                   int H, int L, Src src, float4* __restrict__ dq,
                                                                    float* __restrict__ delta_out) {
 #pragma clang fp contract(off)
+  const DropRng g = drop_source<DROP>(src);
   extern __shared__ float4 attn_smem[];
   float4* sk = attn_smem;
   float4* sv = attn_smem + L;
@@ -161,13 +201,14 @@ __global__ __launch_bounds__(kAttnThreads) void attn_bwd_dq_kernel(const float4*
   }
 }
 
-template <bool DROP>
+template <bool DROP, class Src>
 __global__ __launch_bounds__(kAttnThreads) void attn_bwd_dkv_kernel(const float4* __restrict__ q, const float4* __restrict__ k,
                                                                     const float4* __restrict__ v, const float* __restrict__ lse,
                                                                     const float* __restrict__ delta, const float4* __restrict__ dout,
-                                                                    int H, int L, DropRng g, float4* __restrict__ dk,
+                                                                    int H, int L, Src src, float4* __restrict__ dk,
                                                                     float4* __restrict__ dv) {
 #pragma clang fp contract(off)
+  const DropRng g = drop_source<DROP>(src);
   extern __shared__ float4 attn_smem[];
   float4* sq = attn_smem;                                   // q_i / sqrt(dh)
   float4* sdo = attn_smem + L;
@@ -207,8 +248,9 @@ __global__ __launch_bounds__(kAttnThreads) void attn_bwd_dkv_kernel(const float4
 
 // ---- ELU -> dropout ---------------------------------------------------------------------------------------------------------------------
 // one thread = one quad of the flat index = one Philox call
-template <bool DROP>
-__global__ __launch_bounds__(256) void elu_dropout_fwd_kernel(const float* __restrict__ x, size_t n, DropRng g, float* __restrict__ out) {
+template <bool DROP, class Src>
+__global__ __launch_bounds__(256) void elu_dropout_fwd_kernel(const float* __restrict__ x, size_t n, Src src, float* __restrict__ out) {
+  const DropRng g = drop_source<DROP>(src);
   const size_t quad = (size_t)blockIdx.x * 256 + threadIdx.x, e0 = quad * 4;
   if (e0 >= n) return;
   uint4 r = make_uint4(0, 0, 0, 0);
@@ -224,9 +266,10 @@ __global__ __launch_bounds__(256) void elu_dropout_fwd_kernel(const float* __res
   }
 }
 
-template <bool DROP>
-__global__ __launch_bounds__(256) void elu_dropout_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x, size_t n, DropRng g,
+template <bool DROP, class Src>
+__global__ __launch_bounds__(256) void elu_dropout_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x, size_t n, Src src,
                                                               float* __restrict__ dx) {
+  const DropRng g = drop_source<DROP>(src);
   const size_t quad = (size_t)blockIdx.x * 256 + threadIdx.x, e0 = quad * 4;
   if (e0 >= n) return;
   uint4 r = make_uint4(0, 0, 0, 0);
@@ -264,16 +307,35 @@ __global__ __launch_bounds__(256) void glu_res_bwd_kernel(const float* __restric
   dab[m * 2 * Cc + Cc + c] = d * a * s * (1.0f - s);
 }
 
-bool drop_rng(const char* what, float p_drop, uint64_t seed, uint64_t offset, DropRng* g) {
+bool drop_p_ok(const char* what, float p_drop) {
   if (!(p_drop >= 0.f && p_drop < 1.f)) {
     set_error("%s: p_drop %g outside [0, 1)", what, (double)p_drop);
     return false;
   }
-  g->key = make_uint2((uint32_t)seed, (uint32_t)(seed >> 32));
-  g->off_lo = (uint32_t)offset;
-  g->off_hi = (uint32_t)(offset >> 32);
-  g->p = p_drop;
-  g->scale = 1.0f / (1.0f - p_drop);
+  return true;
+}
+
+bool drop_rng(const char* what, float p_drop, uint64_t seed, uint64_t offset, DropRng* g) {
+  if (!drop_p_ok(what, p_drop)) return false;
+  *g = drop_rng_of(seed, offset, p_drop, 1.0f / (1.0f - p_drop));
+  return true;
+}
+
+// the source of a *_dev launch; p_drop = 0 never reads seed_ctr, so it may be null then
+bool drop_dev(const char* what, float p_drop, const int64_t* seed_ctr, uint32_t ordinal, DropDev* d) {
+  if (!drop_p_ok(what, p_drop)) return false;
+  if (ordinal >= kDropMaxOrdinal) {
+    set_error("%s: dropout ordinal %u does not fit the step offset (< %u)", what, ordinal, kDropMaxOrdinal);
+    return false;
+  }
+  if (p_drop > 0.f && (seed_ctr == nullptr || ((uintptr_t)seed_ctr & 7) != 0)) {
+    set_error("%s: seed_ctr is null or not 8-byte aligned", what);
+    return false;
+  }
+  d->seed_ctr = seed_ctr;
+  d->ordinal = ordinal;
+  d->p = p_drop;
+  d->scale = 1.0f / (1.0f - p_drop);
   return true;
 }
 
@@ -301,20 +363,88 @@ extern "C" size_t evae_causal_attn_lds_bytes(int L, int pass) {
   return pass == 0 ? (size_t)L * 2 * sizeof(float4) : (size_t)L * (2 * sizeof(float4) + 2 * sizeof(float));
 }
 
+// The launches behind the host-argument entry points (Src = DropRng) and the *_dev ones (Src = DropDev): one body each.
+namespace {
+
+template <class Src>
+int attn_fwd_launch(const char* what, const float* q, const float* k, const float* v, int B, int H, int L, const Src& g, float* out,
+                    float* lse, evae_stream_t s) {
+  if (B == 0) return EVAE_OK;
+  EVAE_REQUIRE(q && k && v && out && lse && aligned16(q, k, v, out), "%s: null or unaligned pointer", what);
+  const size_t lds = evae_causal_attn_lds_bytes(L, 0);
+  const float4 *q4 = (const float4*)q, *k4 = (const float4*)k, *v4 = (const float4*)v;
+  if (g.p > 0.f)
+    attn_fwd_kernel<true><<<B * H, kAttnThreads, lds, (hipStream_t)s>>>(q4, k4, v4, H, L, g, (float4*)out, lse);
+  else
+    attn_fwd_kernel<false><<<B * H, kAttnThreads, lds, (hipStream_t)s>>>(q4, k4, v4, H, L, g, (float4*)out, lse);
+  return check_launch(what);
+}
+
+template <class Src>
+int attn_bwd_launch(const char* what, const float* q, const float* k, const float* v, const float* out, const float* lse,
+                    const float* dout, int B, int H, int L, const Src& g, float* delta, float* dq, float* dk, float* dv,
+                    evae_stream_t s) {
+  if (B == 0) return EVAE_OK;
+  EVAE_REQUIRE(q && k && v && out && lse && dout && delta && dq && dk && dv && aligned16(q, k, v, out) && aligned16(dout, dq, dk, dv),
+               "%s: null or unaligned pointer", what);
+  const size_t lds0 = evae_causal_attn_lds_bytes(L, 0), lds1 = evae_causal_attn_lds_bytes(L, 1);
+  const float4 *q4 = (const float4*)q, *k4 = (const float4*)k, *v4 = (const float4*)v, *o4 = (const float4*)out, *d4 = (const float4*)dout;
+  if (g.p > 0.f) {
+    attn_bwd_dq_kernel<true><<<B * H, kAttnThreads, lds0, (hipStream_t)s>>>(q4, k4, v4, o4, lse, d4, H, L, g, (float4*)dq, delta);
+    attn_bwd_dkv_kernel<true><<<B * H, kAttnThreads, lds1, (hipStream_t)s>>>(q4, k4, v4, lse, delta, d4, H, L, g, (float4*)dk, (float4*)dv);
+  } else {
+    attn_bwd_dq_kernel<false><<<B * H, kAttnThreads, lds0, (hipStream_t)s>>>(q4, k4, v4, o4, lse, d4, H, L, g, (float4*)dq, delta);
+    attn_bwd_dkv_kernel<false><<<B * H, kAttnThreads, lds1, (hipStream_t)s>>>(q4, k4, v4, lse, delta, d4, H, L, g, (float4*)dk, (float4*)dv);
+  }
+  return check_launch(what);
+}
+
+template <class Src>
+int elu_dropout_fwd_launch(const char* what, const float* x, size_t n, const Src& g, float* out, evae_stream_t s) {
+  if (n == 0) return EVAE_OK;
+  EVAE_REQUIRE(x && out, "%s: null pointer", what);
+  const size_t nblk = ((n + 3) / 4 + 255) / 256;
+  EVAE_REQUIRE(nblk <= 0x7fffffffu, "%s: too many elements", what);
+  if (g.p > 0.f)
+    elu_dropout_fwd_kernel<true><<<(unsigned)nblk, 256, 0, (hipStream_t)s>>>(x, n, g, out);
+  else
+    elu_dropout_fwd_kernel<false><<<(unsigned)nblk, 256, 0, (hipStream_t)s>>>(x, n, g, out);
+  return check_launch(what);
+}
+
+template <class Src>
+int elu_dropout_bwd_launch(const char* what, const float* dy, const float* x, size_t n, const Src& g, float* dx, evae_stream_t s) {
+  if (n == 0) return EVAE_OK;
+  EVAE_REQUIRE(dy && x && dx, "%s: null pointer", what);
+  const size_t nblk = ((n + 3) / 4 + 255) / 256;
+  EVAE_REQUIRE(nblk <= 0x7fffffffu, "%s: too many elements", what);
+  if (g.p > 0.f)
+    elu_dropout_bwd_kernel<true><<<(unsigned)nblk, 256, 0, (hipStream_t)s>>>(dy, x, n, g, dx);
+  else
+    elu_dropout_bwd_kernel<false><<<(unsigned)nblk, 256, 0, (hipStream_t)s>>>(dy, x, n, g, dx);
+  return check_launch(what);
+}
+
+}  // namespace
+
+extern "C" uint64_t evae_dropout_step_offset(uint64_t counter, uint32_t ordinal) {
+  return ordinal < kDropMaxOrdinal ? drop_step_offset(counter, ordinal) : 0;
+}
+
 extern "C" int evae_causal_attn_fwd(const float* q, const float* k, const float* v, int B, int H, int L, int dh, float p_drop,
                                     uint64_t seed, uint64_t offset, float* out, float* lse, evae_stream_t s) {
   if (int rc = attn_check("causal_attn_fwd", B, H, L, dh)) return rc;
   DropRng g;
   if (!drop_rng("causal_attn_fwd", p_drop, seed, offset, &g)) return EVAE_EINVAL;
-  if (B == 0) return EVAE_OK;
-  EVAE_REQUIRE(q && k && v && out && lse && aligned16(q, k, v, out), "causal_attn_fwd: null or unaligned pointer");
-  const size_t lds = evae_causal_attn_lds_bytes(L, 0);
-  const float4 *q4 = (const float4*)q, *k4 = (const float4*)k, *v4 = (const float4*)v;
-  if (p_drop > 0.f)
-    attn_fwd_kernel<true><<<B * H, kAttnThreads, lds, (hipStream_t)s>>>(q4, k4, v4, H, L, g, (float4*)out, lse);
-  else
-    attn_fwd_kernel<false><<<B * H, kAttnThreads, lds, (hipStream_t)s>>>(q4, k4, v4, H, L, g, (float4*)out, lse);
-  return check_launch("causal_attn_fwd");
+  return attn_fwd_launch("causal_attn_fwd", q, k, v, B, H, L, g, out, lse, s);
+}
+
+extern "C" int evae_causal_attn_fwd_dev(const float* q, const float* k, const float* v, int B, int H, int L, int dh, float p_drop,
+                                        const int64_t* seed_ctr, uint32_t ordinal, float* out, float* lse, evae_stream_t s) {
+  if (int rc = attn_check("causal_attn_fwd_dev", B, H, L, dh)) return rc;
+  DropDev g;
+  if (!drop_dev("causal_attn_fwd_dev", p_drop, seed_ctr, ordinal, &g)) return EVAE_EINVAL;
+  return attn_fwd_launch("causal_attn_fwd_dev", q, k, v, B, H, L, g, out, lse, s);
 }
 
 extern "C" int evae_causal_attn_bwd(const float* q, const float* k, const float* v, const float* out, const float* lse,
@@ -323,48 +453,43 @@ extern "C" int evae_causal_attn_bwd(const float* q, const float* k, const float*
   if (int rc = attn_check("causal_attn_bwd", B, H, L, dh)) return rc;
   DropRng g;
   if (!drop_rng("causal_attn_bwd", p_drop, seed, offset, &g)) return EVAE_EINVAL;
-  if (B == 0) return EVAE_OK;
-  EVAE_REQUIRE(q && k && v && out && lse && dout && delta && dq && dk && dv && aligned16(q, k, v, out) && aligned16(dout, dq, dk, dv),
-               "causal_attn_bwd: null or unaligned pointer");
-  const size_t lds0 = evae_causal_attn_lds_bytes(L, 0), lds1 = evae_causal_attn_lds_bytes(L, 1);
-  const float4 *q4 = (const float4*)q, *k4 = (const float4*)k, *v4 = (const float4*)v, *o4 = (const float4*)out, *d4 = (const float4*)dout;
-  if (p_drop > 0.f) {
-    attn_bwd_dq_kernel<true><<<B * H, kAttnThreads, lds0, (hipStream_t)s>>>(q4, k4, v4, o4, lse, d4, H, L, g, (float4*)dq, delta);
-    attn_bwd_dkv_kernel<true><<<B * H, kAttnThreads, lds1, (hipStream_t)s>>>(q4, k4, v4, lse, delta, d4, H, L, g, (float4*)dk, (float4*)dv);
-  } else {
-    attn_bwd_dq_kernel<false><<<B * H, kAttnThreads, lds0, (hipStream_t)s>>>(q4, k4, v4, o4, lse, d4, H, L, g, (float4*)dq, delta);
-    attn_bwd_dkv_kernel<false><<<B * H, kAttnThreads, lds1, (hipStream_t)s>>>(q4, k4, v4, lse, delta, d4, H, L, g, (float4*)dk, (float4*)dv);
-  }
-  return check_launch("causal_attn_bwd");
+  return attn_bwd_launch("causal_attn_bwd", q, k, v, out, lse, dout, B, H, L, g, delta, dq, dk, dv, s);
+}
+
+extern "C" int evae_causal_attn_bwd_dev(const float* q, const float* k, const float* v, const float* out, const float* lse,
+                                        const float* dout, int B, int H, int L, int dh, float p_drop, const int64_t* seed_ctr,
+                                        uint32_t ordinal, float* delta, float* dq, float* dk, float* dv, evae_stream_t s) {
+  if (int rc = attn_check("causal_attn_bwd_dev", B, H, L, dh)) return rc;
+  DropDev g;
+  if (!drop_dev("causal_attn_bwd_dev", p_drop, seed_ctr, ordinal, &g)) return EVAE_EINVAL;
+  return attn_bwd_launch("causal_attn_bwd_dev", q, k, v, out, lse, dout, B, H, L, g, delta, dq, dk, dv, s);
 }
 
 extern "C" int evae_elu_dropout_fwd(const float* x, size_t n, float p_drop, uint64_t seed, uint64_t offset, float* out, evae_stream_t s) {
   DropRng g;
   if (!drop_rng("elu_dropout_fwd", p_drop, seed, offset, &g)) return EVAE_EINVAL;
-  if (n == 0) return EVAE_OK;
-  EVAE_REQUIRE(x && out, "elu_dropout_fwd: null pointer");
-  const size_t nblk = ((n + 3) / 4 + 255) / 256;
-  EVAE_REQUIRE(nblk <= 0x7fffffffu, "elu_dropout_fwd: too many elements");
-  if (p_drop > 0.f)
-    elu_dropout_fwd_kernel<true><<<(unsigned)nblk, 256, 0, (hipStream_t)s>>>(x, n, g, out);
-  else
-    elu_dropout_fwd_kernel<false><<<(unsigned)nblk, 256, 0, (hipStream_t)s>>>(x, n, g, out);
-  return check_launch("elu_dropout_fwd");
+  return elu_dropout_fwd_launch("elu_dropout_fwd", x, n, g, out, s);
+}
+
+extern "C" int evae_elu_dropout_fwd_dev(const float* x, size_t n, float p_drop, const int64_t* seed_ctr, uint32_t ordinal, float* out,
+                                        evae_stream_t s) {
+  DropDev g;
+  if (!drop_dev("elu_dropout_fwd_dev", p_drop, seed_ctr, ordinal, &g)) return EVAE_EINVAL;
+  return elu_dropout_fwd_launch("elu_dropout_fwd_dev", x, n, g, out, s);
 }
 
 extern "C" int evae_elu_dropout_bwd(const float* dy, const float* x, size_t n, float p_drop, uint64_t seed, uint64_t offset, float* dx,
                                     evae_stream_t s) {
   DropRng g;
   if (!drop_rng("elu_dropout_bwd", p_drop, seed, offset, &g)) return EVAE_EINVAL;
-  if (n == 0) return EVAE_OK;
-  EVAE_REQUIRE(dy && x && dx, "elu_dropout_bwd: null pointer");
-  const size_t nblk = ((n + 3) / 4 + 255) / 256;
-  EVAE_REQUIRE(nblk <= 0x7fffffffu, "elu_dropout_bwd: too many elements");
-  if (p_drop > 0.f)
-    elu_dropout_bwd_kernel<true><<<(unsigned)nblk, 256, 0, (hipStream_t)s>>>(dy, x, n, g, dx);
-  else
-    elu_dropout_bwd_kernel<false><<<(unsigned)nblk, 256, 0, (hipStream_t)s>>>(dy, x, n, g, dx);
-  return check_launch("elu_dropout_bwd");
+  return elu_dropout_bwd_launch("elu_dropout_bwd", dy, x, n, g, dx, s);
+}
+
+extern "C" int evae_elu_dropout_bwd_dev(const float* dy, const float* x, size_t n, float p_drop, const int64_t* seed_ctr, uint32_t ordinal,
+                                        float* dx, evae_stream_t s) {
+  DropDev g;
+  if (!drop_dev("elu_dropout_bwd_dev", p_drop, seed_ctr, ordinal, &g)) return EVAE_EINVAL;
+  return elu_dropout_bwd_launch("elu_dropout_bwd_dev", dy, x, n, g, dx, s);
 }
 
 extern "C" int evae_glu_res_fwd(const float* ab, const float* x, int64_t M, int C, float* out, evae_stream_t s) {

@@ -183,6 +183,11 @@ SIGNATURES = {
     "evae_pixel_decode": (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
     "evae_elu_dropout_fwd": (_i, [_p, _z, _f, _q, _q, _p, _p]),
     "evae_elu_dropout_bwd": (_i, [_p, _p, _z, _f, _q, _q, _p, _p]),
+    "evae_dropout_step_offset": (_q, [_q, _u]),
+    "evae_causal_attn_fwd_dev": (_i, [_p, _p, _p, _i, _i, _i, _i, _f, _p, _u, _p, _p, _p]),
+    "evae_causal_attn_bwd_dev": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _p, _u, _p, _p, _p, _p, _p]),
+    "evae_elu_dropout_fwd_dev": (_i, [_p, _z, _f, _p, _u, _p, _p]),
+    "evae_elu_dropout_bwd_dev": (_i, [_p, _p, _z, _f, _p, _u, _p, _p]),
     "evae_glu_res_fwd": (_i, [_p, _p, _l, _i, _p, _p]),
     "evae_glu_res_bwd": (_i, [_p, _p, _l, _i, _p, _p]),
     "evae_conv2d_cl_res_supported": (_i, [_p]),

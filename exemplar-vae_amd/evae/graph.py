@@ -23,6 +23,13 @@ ops.MixtureLogP's launches, the ones an eager step issues.  A standard-normal-pr
 takes the same runner: `vae` captures the one-node, one-stream step of evae/fused_std.py (which reads the prologue's eps and beta from
 the hand-off), `hvae_2level` its modular path.
 
+A pixelcnn step (utils/training.py::pixelcnn_step_eligible: the exact exemplar prior on one device) runs its modular path through
+the same runner.  Its PixelSNAIL decoder draws eight dropout masks per step; a (seed, offset) pair passed as launch arguments would be
+frozen into the captured nodes, so inside a runner's step the dropout launches are the *_dev ones of csrc/evae_attn.hip: they read
+[seed, step counter] from this control block (the prologue's `seed_ctr` field) and carry only the mask's ordinal within the step
+(evae/handoff.py::DropoutSource, installed by _step_scope).  Every replay therefore draws new masks, and a warm-up call, a replay
+and step_eagerly of one call number draw the same ones.  The model's two eps draws are torch.randn on the registered generator.
+
 What the model and the fused node have to know about the step that is running -- its gather list, the distinct-row tables, the
 prologue's eps, the promise that the only backward is loss.backward(ones), what the head launch already did for them -- travels
 on ONE object, evae/handoff.py's StepHandoff: _step_scope installs it for the length of a call and takes it away again, so
@@ -61,6 +68,8 @@ if _REFRESH_PROF:
 
 
 class GraphedTrainStep:
+    keep_graph = False     # True before the capture: the hipGraph_t outlives its instantiation, for node_count() (tools/)
+
     def __init__(self, model, optimizer, dataset, batch_size, dynamic_binarization, warmup_steps=3):
         a = model.args
         self.model, self.opt, self.dataset = model, optimizer, dataset
@@ -211,6 +220,17 @@ class GraphedTrainStep:
         self.warmup_steps = max(2, warmup_steps)    # call 0 learns the optimizer's participants, call 1 warms the captured form
         self._calls = 0
         self.replays = 0           # steps that were replays of the captured graph
+
+    def node_count(self):
+        """Nodes of the captured step's graph (kernel launches, copies, fills: what a replay issues), asked of the HIP runtime torch
+        loaded.  Only for a runner whose class or instance had keep_graph = True before the capture."""
+        assert self.graph is not None and self.keep_graph, "node_count: no kept graph"
+        hip = C.CDLL("libamdhip64.so")
+        n = C.c_size_t(0)
+        rc = hip.hipGraphGetNodes(C.c_void_p(self.graph.raw_cuda_graph()), None, C.byref(n))
+        if rc != 0:
+            raise RuntimeError("hipGraphGetNodes failed (%d)" % rc)
+        return int(n.value)
 
     def reset_totals(self):
         self.totals.zero_()
@@ -428,6 +448,10 @@ class GraphedTrainStep:
                     self._refresh(*refresh)
                 h.eps = self.eps_buf if self.by_index else None
                 h.batch_staged = bool(self.by_index and self.u8)
+                if self.model.args.model_name == 'pixelcnn':
+                    # the decoder's eight dropout masks: Philox words from the control block's [seed, step counter], ordinals from 0
+                    # in every scope -- a warm-up call, a replay, step_eagerly and the every-draw step of one call number draw alike
+                    h.dropout = handoff.DropoutSource(self.seed_ctr)
                 yield h
             finally:
                 if refresh is not None and self._handover and self.by_index:
@@ -482,7 +506,7 @@ class GraphedTrainStep:
                     return self.out
                 torch.cuda.synchronize()
                 main_stream = torch.cuda.current_stream()
-                graph = torch.cuda.CUDAGraph()
+                graph = torch.cuda.CUDAGraph(keep_graph=True) if self.keep_graph else torch.cuda.CUDAGraph()
                 # with RCCL in the step its watchdog thread polls events while we capture: thread-local capture mode
                 # keeps those calls from invalidating the capture
                 mode = "thread_local" if shard.is_active() else "global"
@@ -490,6 +514,8 @@ class GraphedTrainStep:
                 try:
                     with torch.cuda.graph(graph, capture_error_mode=mode):
                         self._body()
+                    if self.keep_graph:
+                        graph.instantiate()      # (a kept graph is not instantiated by the end of its capture)
                     self.opt.finish_capture(self._adam_tables)
                     self.graph = graph
                 except Exception as e:           # an op of this model that cannot be captured: eager from here on

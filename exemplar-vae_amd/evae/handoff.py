@@ -8,8 +8,22 @@ import contextlib
 _current = None
 
 
+class DropoutSource:
+    """The dropout masks of ONE step of a runner: `seed_ctr`, the two device words [seed, step counter] of its control block, and
+    the ordinal the next mask of the step takes (0, 1, 2, ... in the order the forward pass asks; a backward pass reuses the
+    ordinal of its forward, evae/ops.py).  A replayed launch carries the pointer and its ordinal; the counter is the replay's."""
+    __slots__ = ("seed_ctr", "ordinal")
+
+    def __init__(self, seed_ctr):
+        self.seed_ctr, self.ordinal = seed_ctr, 0
+
+    def take(self):
+        o, self.ordinal = self.ordinal, self.ordinal + 1
+        return o
+
+
 class StepHandoff:
-    __slots__ = ("rows", "n_rows", "dedup", "eps", "batch_staged", "unit_upstream", "beta", "prep", "wt", "p6", "p6_images")
+    __slots__ = ("rows", "n_rows", "dedup", "eps", "batch_staged", "unit_upstream", "beta", "prep", "wt", "p6", "p6_images", "dropout")
 
     def __init__(self, rows=None, n_rows=0, dedup=None):
         self.rows, self.n_rows = rows, n_rows   # gather list [this rank's exemplar rows | staging rows of the batch], rows of its head
@@ -24,6 +38,9 @@ class StepHandoff:
         self.prep = self.wt = self.p6 = None
         # back-channel: (w2h, w2g, H, forward image, data-gradient image) the node's pre-split layer 2 used in this step
         self.p6_images = None
+        # a DropoutSource: the step's dropout calls take their masks from the control block (the pixelcnn decoder); None: the
+        # process counter of ops.dropout_rng()
+        self.dropout = None
 
     def take_prep(self, prep, w1h, w1g):
         tok, self.prep = self.prep, None

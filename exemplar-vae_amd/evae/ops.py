@@ -2,6 +2,7 @@
 torch.autograd.Function wrappers the reference-named modules (utils/nn.py, utils/distributions.py,
 models/BaseModel.py) are built from.  PyTorch here is device memory, streams and autograd plumbing;
 all arithmetic on [rows x features] data happens in libevae_hip.so.  No CPU fallback."""
+import collections
 import ctypes as C
 import os
 
@@ -2398,13 +2399,42 @@ def dropout_rng():
     return int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF, off
 
 
+class StepRng(collections.namedtuple("StepRng", "seed_ctr ordinal")):
+    """A dropout mask whose Philox words come from DEVICE memory (the *_dev launches of csrc/evae_attn.hip): `seed_ctr`, an int64
+    device tensor [seed, step counter] -- the field of that name in a step runner's control block (evae/graph.py) --, and the
+    ordinal of the mask within the step.  The mask is that of the host pair (seed, dropout_step_offset(counter, ordinal))."""
+    __slots__ = ()
+
+
+def dropout_step_offset(counter, ordinal):
+    """the Philox offset of mask `ordinal` of step `counter`: the library's evae_dropout_step_offset, the one statement of it"""
+    if not 0 <= int(ordinal) < 65536:
+        raise _lib.EvaeError("dropout ordinal %d does not fit the step offset (< 65536)" % int(ordinal))
+    return int(_lib.load().evae_dropout_step_offset(int(counter) & 0xFFFFFFFFFFFFFFFF, int(ordinal)))
+
+
 def _rng_args(p_drop, rng):
-    """p_drop = 0 draws nothing (and leaves the counter alone)"""
+    """(p_drop, seed, offset, seed_ctr) of one dropout call.  p_drop = 0 draws nothing (and leaves every counter alone).  Inside a
+    step whose runner installed a dropout source (evae/handoff.py) a call without an explicit rng takes the source's next ordinal:
+    seed_ctr is its device block, `offset` carries the ordinal, and the process counter of dropout_rng() stays where it is.  An
+    explicit rng is a host pair (seed, offset) or a StepRng."""
     p_drop = float(p_drop)
     if p_drop == 0.0:
-        return 0.0, 0, 0
+        return 0.0, 0, 0, None
+    if rng is None:
+        h = handoff.current()
+        if h is not None and h.dropout is not None:
+            rng = StepRng(h.dropout.seed_ctr, h.dropout.take())
+    if isinstance(rng, StepRng):
+        return p_drop, 0, int(rng.ordinal), rng.seed_ctr
     seed, offset = dropout_rng() if rng is None else rng
-    return p_drop, int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFFFFFFFFFF
+    return p_drop, int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFFFFFFFFFF, None
+
+
+def _seed_ctr_ptr(seed_ctr):
+    if not (seed_ctr.is_cuda and seed_ctr.dtype == torch.int64 and seed_ctr.numel() >= 2 and seed_ctr.is_contiguous()):
+        raise _lib.EvaeError("dropout: seed_ctr must be a contiguous int64 device tensor [seed, step counter]")
+    return _p(seed_ctr)
 
 
 def causal_attn_max_len():
@@ -2413,10 +2443,11 @@ def causal_attn_max_len():
 
 class CausalAttnFn(torch.autograd.Function):
     """Causal attention of reference utils/nn.py:351-359 on projected rows: q, k, v [B*L, H*dh] -> out [B*L, H*dh].  Saves q, k, v,
-    out and one log-sum-exp per row; the dropout mask is regenerated from (seed, offset) in the backward pass."""
+    out and one log-sum-exp per row; the dropout mask is regenerated in the backward pass from (seed, offset), or, with a device
+    source, from the same seed_ctr block and the SAME ordinal (kept in ctx: it is never drawn again)."""
 
     @staticmethod
-    def forward(ctx, q, k, v, B, L, H, p_drop, seed, offset):
+    def forward(ctx, q, k, v, B, L, H, p_drop, seed, offset, seed_ctr):
         lib = _lib.load()
         _need_cuda(q, k, v)
         q, k, v = _f32(q), _f32(k), _f32(v)
@@ -2425,27 +2456,36 @@ class CausalAttnFn(torch.autograd.Function):
         dh = q.shape[1] // H
         out = torch.empty_like(q)
         lse = torch.empty((B, H, L), device=q.device)
-        _lib.check(lib.evae_causal_attn_fwd(_p(q), _p(k), _p(v), B, H, L, dh, p_drop, seed, offset, _p(out), _p(lse), _stream()),
-                   "evae_causal_attn_fwd")
+        if seed_ctr is None:
+            _lib.check(lib.evae_causal_attn_fwd(_p(q), _p(k), _p(v), B, H, L, dh, p_drop, seed, offset, _p(out), _p(lse), _stream()),
+                       "evae_causal_attn_fwd")
+        else:
+            _lib.check(lib.evae_causal_attn_fwd_dev(_p(q), _p(k), _p(v), B, H, L, dh, p_drop, _seed_ctr_ptr(seed_ctr), offset, _p(out),
+                                                    _p(lse), _stream()), "evae_causal_attn_fwd_dev")
         ctx.save_for_backward(q, k, v, out, lse)
-        ctx.cfg = (B, L, H, dh, p_drop, seed, offset)
+        ctx.cfg = (B, L, H, dh, p_drop, seed, offset, seed_ctr)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         lib = _lib.load()
         q, k, v, out, lse = ctx.saved_tensors
-        B, L, H, dh, p_drop, seed, offset = ctx.cfg
+        B, L, H, dh, p_drop, seed, offset, seed_ctr = ctx.cfg
         dout = _f32(dout)
         dq, dk, dv = torch.empty_like(q), torch.empty_like(q), torch.empty_like(q)
         delta = torch.empty_like(lse)                # scratch: the row pass hands delta_i to the column pass
-        _lib.check(lib.evae_causal_attn_bwd(_p(q), _p(k), _p(v), _p(out), _p(lse), _p(dout), B, H, L, dh, p_drop, seed, offset,
-                                            _p(delta), _p(dq), _p(dk), _p(dv), _stream()), "evae_causal_attn_bwd")
-        return dq, dk, dv, None, None, None, None, None, None
+        if seed_ctr is None:
+            _lib.check(lib.evae_causal_attn_bwd(_p(q), _p(k), _p(v), _p(out), _p(lse), _p(dout), B, H, L, dh, p_drop, seed, offset,
+                                                _p(delta), _p(dq), _p(dk), _p(dv), _stream()), "evae_causal_attn_bwd")
+        else:
+            _lib.check(lib.evae_causal_attn_bwd_dev(_p(q), _p(k), _p(v), _p(out), _p(lse), _p(dout), B, H, L, dh, p_drop,
+                                                    _seed_ctr_ptr(seed_ctr), offset, _p(delta), _p(dq), _p(dk), _p(dv), _stream()),
+                       "evae_causal_attn_bwd_dev")
+        return dq, dk, dv, None, None, None, None, None, None, None
 
 
 def causal_attn(q, k, v, B, L, H, p_drop=0.0, rng=None):
-    """rng = (seed, offset): an explicit mask (tests); None: dropout_rng()"""
+    """rng = (seed, offset) or a StepRng: an explicit mask (tests); None: the step's dropout source, else dropout_rng()"""
     return CausalAttnFn.apply(q, k, v, int(B), int(L), int(H), *_rng_args(p_drop, rng))
 
 
@@ -2460,26 +2500,35 @@ class EluDropoutFn(torch.autograd.Function):
     """dropout(ELU(x)) in one launch, the mask over the flat storage index; the output keeps x's layout"""
 
     @staticmethod
-    def forward(ctx, x, p_drop, seed, offset):
+    def forward(ctx, x, p_drop, seed, offset, seed_ctr):
         lib = _lib.load()
         _need_cuda(x)
         x = _dense(x.float())
         out = torch.empty_like(x)                    # (preserve_format: the same strides)
-        _lib.check(lib.evae_elu_dropout_fwd(_p(x), x.numel(), p_drop, seed, offset, _p(out), _stream()), "evae_elu_dropout_fwd")
+        if seed_ctr is None:
+            _lib.check(lib.evae_elu_dropout_fwd(_p(x), x.numel(), p_drop, seed, offset, _p(out), _stream()), "evae_elu_dropout_fwd")
+        else:
+            _lib.check(lib.evae_elu_dropout_fwd_dev(_p(x), x.numel(), p_drop, _seed_ctr_ptr(seed_ctr), offset, _p(out), _stream()),
+                       "evae_elu_dropout_fwd_dev")
         ctx.save_for_backward(x)
-        ctx.cfg = (p_drop, seed, offset)
+        ctx.cfg = (p_drop, seed, offset, seed_ctr)
         return out
 
     @staticmethod
     def backward(ctx, dy):
         lib = _lib.load()
         x, = ctx.saved_tensors
+        p_drop, seed, offset, seed_ctr = ctx.cfg
         dy = dy.float()
         if dy.stride() != x.stride():
             dy = torch.empty_like(x).copy_(dy)
         dx = torch.empty_like(x)
-        _lib.check(lib.evae_elu_dropout_bwd(_p(dy), _p(x), x.numel(), *ctx.cfg, _p(dx), _stream()), "evae_elu_dropout_bwd")
-        return dx, None, None, None
+        if seed_ctr is None:
+            _lib.check(lib.evae_elu_dropout_bwd(_p(dy), _p(x), x.numel(), p_drop, seed, offset, _p(dx), _stream()), "evae_elu_dropout_bwd")
+        else:
+            _lib.check(lib.evae_elu_dropout_bwd_dev(_p(dy), _p(x), x.numel(), p_drop, _seed_ctr_ptr(seed_ctr), offset, _p(dx), _stream()),
+                       "evae_elu_dropout_bwd_dev")
+        return dx, None, None, None, None
 
 
 def elu_dropout(x, p_drop=0.0, rng=None):

@@ -77,17 +77,29 @@ def standard_step_eligible(a):
             and not bool(getattr(a, 'shard_exemplars', False)))
 
 
+def pixelcnn_step_eligible(a):
+    """Whether a pixelcnn training step of the configuration `a` is captured -- a function of the arguments alone: the exact
+    exemplar prior on one device.  The approximate prior, the VampPrior and the standard-normal prior of this model stay eager
+    (their captured form has not been validated with its decoder), and so does any configuration that asks for sharding.  Its
+    dropout masks take their Philox words from the runner's control block (evae/graph.py), so every replay draws new ones."""
+    return (a.model_name == 'pixelcnn' and a.prior == 'exemplar_prior' and a.approximate_prior is False
+            and not bool(getattr(a, 'shard_exemplars', False)))
+
+
 def _graphed_step(args, model, optimizer, train_loader):
     """The captured-step runner for this (model, optimizer, dataset), or None when the configuration is not
     a graph-capturable one or args.use_hip_graph is False.  Capturable: the exemplar prior (below), and the VampPrior of the
     dense models on one device (vampprior_step_eligible; convolutional models, and every process of a torch.distributed group
     of several ranks, step eagerly) -- its step runs the modular autograd path with no exemplar rows in the runner (evae/graph.py);
-    the standard-normal prior under the same condition (standard_step_eligible), `vae` through the node of evae/fused_std.py."""
+    the standard-normal prior under the same condition (standard_step_eligible), `vae` through the node of evae/fused_std.py;
+    pixelcnn with the exact exemplar prior on one device (pixelcnn_step_eligible), every other pixelcnn configuration eagerly."""
     if not getattr(args, 'use_hip_graph', True) or not str(args.device).startswith('cuda'):
         return None
     a = model.args
-    if a.model_name == 'pixelcnn':
-        return None        # eager: its dropout masks take their Philox offset from a host counter, which a replay would freeze
+    if a.model_name == 'pixelcnn' and not (pixelcnn_step_eligible(a) and not shard.is_active()):
+        # eager: only the exact exemplar prior on one device is captured (its dropout masks read the runner's control block; an
+        # eager step's take their Philox offset from the host counter of evae.ops.dropout_rng)
+        return None
     # capturable: the exact exemplar prior, and the approximate (cache + top-k) one on a single device with the leave-one-out
     # mask on -- its exemplar union lives in a fixed list of B * k slots with masked repeats instead of a data-dependent
     # `unique` (models/BaseModel.py::get_approximate_nearest_exemplars; dense encoders only: a convolutional encoder would

@@ -530,6 +530,15 @@ int evae_conv2d_cl_bwd_data_res(const float* dy, const float* w, const evae_conv
  * word e % 4 of quad e / 4, counter (quad_lo, quad_hi, offset_lo, offset_hi), key (seed_lo, seed_hi), keep <=> u01(word) >= p_drop,
  * kept values times 1 / (1 - p_drop).  Attention: e = ((b H + h) L + i) L + j.  Element-wise: e = the flat index.
  *
+ * The *_dev entry points are the same launches with the two Philox words taken from DEVICE memory, for a step that is replayed from
+ * a captured hipGraph (evae/graph.py): in place of (seed, offset) they take `seed_ctr`, a device pointer to the two int64 words
+ * [seed, step counter] (8-byte aligned), and `ordinal`, the number of this mask within the step, a launch-time constant.  Each kernel
+ * loads the two words once at entry; key = (seed_lo, seed_hi), offset = evae_dropout_step_offset(counter, ordinal), and from there
+ * the mask code above.  The forward and the backward launch of one operator read the same two words.
+ *   evae_dropout_step_offset(counter, ordinal) = 2^63 | (counter mod 2^47) << 16 | ordinal     for ordinal < 65536
+ * (0, which no step offset equals, for any other ordinal; the launches answer such an ordinal with EVAE_EINVAL).  Bit 63 keeps these
+ * offsets apart from a host counter's 0, 1, 2, ...  p_drop = 0 never reads seed_ctr (it may be NULL then).
+ *
  *   evae_elu_dropout_fwd   out = dropout(ELU(x))                 (utils/nn.py:298-299; p_drop = 0: the plain ELU of :293)
  *   evae_elu_dropout_bwd   dx = dy * mask/(1-p) * ELU'(x)
  *   evae_glu_res_fwd       out[m, c] = ab[m, c] * sigmoid(ab[m, C + c]) + x[m, c]     (GLU over channels + residual, :307-308;
@@ -545,6 +554,16 @@ int evae_causal_attn_bwd(const float* q, const float* k, const float* v, const f
 int evae_elu_dropout_fwd(const float* x, size_t n, float p_drop, uint64_t seed, uint64_t offset, float* out, evae_stream_t stream);
 int evae_elu_dropout_bwd(const float* dy, const float* x, size_t n, float p_drop, uint64_t seed, uint64_t offset, float* dx,
                          evae_stream_t stream);
+uint64_t evae_dropout_step_offset(uint64_t counter, uint32_t ordinal);
+int evae_causal_attn_fwd_dev(const float* q, const float* k, const float* v, int B, int H, int L, int dh, float p_drop,
+                             const int64_t* seed_ctr, uint32_t ordinal, float* out, float* lse, evae_stream_t stream);
+int evae_causal_attn_bwd_dev(const float* q, const float* k, const float* v, const float* out, const float* lse, const float* dout,
+                             int B, int H, int L, int dh, float p_drop, const int64_t* seed_ctr, uint32_t ordinal, float* delta,
+                             float* dq, float* dk, float* dv, evae_stream_t stream);
+int evae_elu_dropout_fwd_dev(const float* x, size_t n, float p_drop, const int64_t* seed_ctr, uint32_t ordinal, float* out,
+                             evae_stream_t stream);
+int evae_elu_dropout_bwd_dev(const float* dy, const float* x, size_t n, float p_drop, const int64_t* seed_ctr, uint32_t ordinal,
+                             float* dx, evae_stream_t stream);
 int evae_glu_res_fwd(const float* ab, const float* x, int64_t M, int C, float* out, evae_stream_t stream);
 int evae_glu_res_bwd(const float* dout, const float* ab, int64_t M, int C, float* dab, evae_stream_t stream);
 
