@@ -18,7 +18,7 @@
 // position t of every plane and of K / V; it reads positions < t only.  A fresh cache is zeros.  Every value that crosses pixels
 // lives in the cache, in x or in nothing: [0, 784) in several launches over one cache is bit-identical to one launch.
 //
-// Plan: a workgroup of 256 threads owns kPdImages images (G below; 1 in this build) and walks the pixels; image b of a launch
+// Plan: a workgroup of 256 threads owns G images (1, 2 or 4: one kernel instance each, chosen per launch) and walks the pixels; image b of a launch
 // always belongs to block b / G, workgroups never wait for each other, no atomics.  Every layer at one pixel is a matrix-vector
 // product y = W x, K <= 448, O <= 260, for the G images at once: the weights are packed TRANSPOSED ([K][O], O a multiple of 4) so
 // that a thread loads one float4 of 4 outputs per k and feeds 4 x G accumulators; the k range is dealt to n = min(256 / (O/4), 16)
@@ -29,15 +29,23 @@
 // out | mean head: 20 barriers).  The weights (1.64 MB, 7 live taps of 9) stream from L2 once per pixel and workgroup, the cached
 // keys and values (on average 100 KB per image) once per pixel and image: the kernel is bound by what one CU reads from L2.
 //
-// Images per workgroup, measured (decode launch alone, ms, MI355X; EVAE_PD_IMAGES builds of this file):
-//        B =   10    100    400   1024
-//   G = 1     21.3   23.2   52.9  109.4
-//   G = 2     25.3   28.5   33.5   69.8
-//   G = 4     35.1   40.5   43.7   48.5
+// Images per workgroup, measured (whole pixelcnn_generate calls on 'cached', ms, median of 3, MI355X; the three instances of ONE build,
+// tools/pixelsnail_generate_bench.py):
+//        B =   10    100    256    257    384    512    550    768   1024   2048
+//   G = 1     23.8   25.1   30.3   49.5   54.9   57.1   77.0   83.3  110.2  219.3
+//   G = 2     27.3   30.3   34.1   34.0   35.7   36.6   62.4   69.1   71.1  142.1
+//   G = 4     36.3   42.1   44.4   44.1   45.0   45.7   46.5   47.4   50.2   99.1
 // More images amortise the weight stream but lengthen every phase of the chain; fewer use more CUs.  Up to 256 images (one per CU)
-// G = 1 is fastest, and the model's callers generate 25 to 100 images at a time: G = 1.  Beyond 256 images its workgroups queue in
-// rounds and G = 2 (up to 512) or 4 would win.  LDS at G = 1: 43936 bytes (7 taps x 8 planes = 14 KB, four partial-sum regions of
-// 4 KB, 5 KB of vectors, 8 KB of biases); the registers (256 VGPRs + AGPRs) keep it at one workgroup per CU.
+// G = 1 is fastest; beyond that its workgroups queue in rounds, and G = 2 (257 to 512 images: one round of at most 256 workgroups)
+// and G = 4 (from 513) win by far more than three times the spread of the calls: evae_pixel_decode_choose_images below.
+// EVAE_PD_IMAGES (1) is the G of evae_pixel_decode.  The cache of an image does not depend on G; the means do at rounding level (the
+// attention deals 256 / (8 G) lanes to a head).  LDS at G = 1: 43936 bytes (7 taps x 8 planes = 14 KB, four partial-sum regions of
+// 4 KB, 5 KB of vectors, 8 KB of biases), 79424 at G = 2, 150400 at G = 4; the registers (256 VGPRs + 94 / 182 / 228 AGPRs, no
+// scratch) keep every instance at one workgroup per CU.
+//
+// Start pixels (image completion): with uniforms, image b is drawn from pixel start[b] on; before it x is read as given, as in a
+// teacher-forced launch, and only the store of x at the end of the pixel loop is skipped.  One launch with start equals, per image
+// and bit for bit, a teacher-forced launch over [0, start) followed by a sampling one over [start, 784) on the same cache.
 #include "evae_common.h"
 
 namespace evae {
@@ -47,7 +55,7 @@ constexpr int kPdThreads = 256;
 #ifndef EVAE_PD_IMAGES
 #define EVAE_PD_IMAGES 1                   // (1, 2 or 4: the table above)
 #endif
-constexpr int kPdImages = EVAE_PD_IMAGES;    // images per workgroup (evae_pixel_decode_images_per_block): 1, 2 or 4
+constexpr int kPdImages = EVAE_PD_IMAGES;    // the build's default images per workgroup (evae_pixel_decode_images_per_block): 1, 2 or 4
 constexpr int kPdC = 64;                     // channels of the residual stream, of the blocks' inner width and of `out`
 constexpr int kPdSide = 28;
 constexpr int kPdL = kPdSide * kPdSide;
@@ -64,9 +72,10 @@ constexpr size_t kPdKOff = kPdPlanes * kPdPlaneFloats;
 constexpr size_t kPdVOff = kPdKOff + (size_t)kPdL * kPdAttn;
 constexpr size_t kPdCacheFloats = kPdVOff + (size_t)kPdL * kPdAttn;
 constexpr int kPdMaxChunks = 16;
-constexpr int kPdPart = 1024 * kPdImages;    // floats of one partial-sum region: chunks x images x O <= 1024 x images for every product
+constexpr __host__ __device__ int pd_part(int G) { return 1024 * G; }      // floats of one partial-sum region: chunks x images x O <= 1024 x images for every product
 constexpr int kPdRegions = 4;
-static_assert(kPdImages == 1 || kPdImages == 2 || kPdImages == 4, "the attention deals 256 / (8 images) lanes to a head");
+constexpr __host__ __device__ bool pd_images_ok(int G) { return G == 1 || G == 2 || G == 4; }      // the attention deals 256 / (8 images) lanes to a head
+static_assert(pd_images_ok(kPdImages), "EVAE_PD_IMAGES must be 1, 2 or 4");
 
 // the packed buffer: slot s starts at float offset off[s] (a multiple of 4)
 enum PdSlot {
@@ -124,6 +133,7 @@ struct PdParams {
   const float* latent;     // [B][2][784]
   float* x;                // [B][784]
   const float* u;          // [B][784] or null (teacher-forced: x is read only)
+  const int* start;        // [B] or null: with u, image b keeps x[b][t] for t < start[b] and is sampled from there (null: 0 for all)
   float* mean;             // [B][784]
   float* cache;            // [B][kPdCacheFloats]
   int B, t0, t1;
@@ -151,7 +161,10 @@ enum PdVec {
   V_Y = V_H5E + 64,         // out.1
   V_END = V_Y + 64
 };
-constexpr int kPdLdsFloats = kPdImages * (kPdPlanes * kPdK + V_END) + kPdRegions * kPdPart + 64 + kPdBiasMax;      // (+ slot offsets, biases)
+constexpr __host__ __device__ int pd_lds_floats(int G) {      // (+ slot offsets, biases)
+  return G * (kPdPlanes * kPdK + V_END) + kPdRegions * pd_part(G) + 64 + kPdBiasMax;
+}
+static_assert(pd_lds_floats(4) * sizeof(float) <= 160 * 1024, "the largest instance must fit the LDS of a CU");
 
 __device__ __forceinline__ float pd_elu(float v) { return v > 0.f ? v : expm1f(v); }
 __device__ __forceinline__ float pd_sigmoid(float v) { return 1.0f / (1.0f + expf(-v)); }
@@ -212,6 +225,7 @@ template <int G>
 __global__ __launch_bounds__(kPdThreads) void pixel_decode_kernel(PdParams p) {
   extern __shared__ float4 pd_smem[];
   float* taps = reinterpret_cast<float*>(pd_smem);       // [G][8 planes][7 taps][64]
+  constexpr int kPdPart = pd_part(G);
   float* part = taps + G * kPdPlanes * kPdK;             // [4 regions][kPdPart]
   float* vec = part + kPdRegions * kPdPart;              // [G][V_END]
   int* off = reinterpret_cast<int*>(vec + G * V_END);    // the slot offsets (in LDS: 41 values that would otherwise sit in SGPRs)
@@ -223,6 +237,9 @@ __global__ __launch_bounds__(kPdThreads) void pixel_decode_kernel(PdParams p) {
   for (int e = tid; e < p.bias_n; e += kPdThreads) SB[e] = W[p.bias0 + e];
   __syncthreads();
   const float* bg = W + off[PD_BG];
+  // the first pixel the owner thread of image b0 + tid draws (earlier ones are read as given); read once, before the pixel loop
+  int first = 0;
+  if (tid < G && b0 + tid < p.B && p.start != nullptr) first = p.start[b0 + tid];
 
   for (int t = p.t0; t < p.t1; ++t) {
     const int i = t / kPdSide, j = t - i * kPdSide;
@@ -474,7 +491,7 @@ __global__ __launch_bounds__(kPdThreads) void pixel_decode_kernel(PdParams p) {
         const float mu = pd_sigmoid(pd_sum<G, 4>(part, tid, 0) + SB[off[PD_M_B]]);
         const size_t e = (size_t)b * kPdL + t;
         p.mean[e] = mu;
-        if (p.u != nullptr) p.x[e] = p.u[e] < mu ? 1.0f : 0.0f;               // before pixel t + 1 reads it (barrier below)
+        if (p.u != nullptr && t >= first) p.x[e] = p.u[e] < mu ? 1.0f : 0.0f;  // before pixel t + 1 reads it (barrier below)
       }
     }
     __syncthreads();
@@ -486,14 +503,35 @@ __global__ __launch_bounds__(kPdThreads) void pixel_decode_kernel(PdParams p) {
 
 using namespace evae;
 
+namespace {
+template <int G>
+void pd_launch(const PdParams& p, hipStream_t s) {
+  constexpr size_t lds = (size_t)pd_lds_floats(G) * sizeof(float);
+  static bool attr = false;                  // once per instance
+  if (!attr) {
+    (void)hipFuncSetAttribute((const void*)pixel_decode_kernel<G>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    attr = true;
+  }
+  pixel_decode_kernel<G><<<(p.B + G - 1) / G, kPdThreads, lds, s>>>(p);
+}
+}  // namespace
+
 extern "C" int evae_pixel_decode_images_per_block(void) { return kPdImages; }
 extern "C" int evae_pixel_decode_table_len(void) { return kPdHeader + PD_SLOTS; }
 extern "C" size_t evae_pixel_decode_cache_floats(void) { return kPdCacheFloats; }
-extern "C" size_t evae_pixel_decode_lds_bytes(void) { return (size_t)kPdLdsFloats * sizeof(float); }
+extern "C" size_t evae_pixel_decode_lds_bytes(void) { return (size_t)pd_lds_floats(kPdImages) * sizeof(float); }
+extern "C" size_t evae_pixel_decode_lds_bytes_for(int g) { return pd_images_ok(g) ? (size_t)pd_lds_floats(g) * sizeof(float) : 0; }
 extern "C" int evae_pixel_decode_slot_floats(int slot) { return slot >= 0 && slot < PD_SLOTS ? pd_slot_floats(slot) : -1; }
 
-extern "C" int evae_pixel_decode(const float* packed, const int* table, int table_len, const float* latent, float* x, const float* u,
-                                 float* mean, float* cache, int B, int t0, int t1, evae_stream_t s) {
+// The images per workgroup the library picks for a launch of B images (host arithmetic).  A range of B leaves 1 only where the larger
+// G beat 1 at the measured sizes on both of its sides by more than 3 x the larger spread (the table in the header: 257 and 512 for
+// 2; 512, 550 and every larger size for 4, where 2 needs a second round of workgroups from 513 on).
+extern "C" int evae_pixel_decode_choose_images(int B) { return B <= 256 ? 1 : B <= 512 ? 2 : 4; }
+
+extern "C" int evae_pixel_decode_ex(const float* packed, const int* table, int table_len, const float* latent, float* x, const float* u,
+                                    const int* start, float* mean, float* cache, int B, int t0, int t1, int images_per_block,
+                                    evae_stream_t s) {
+  EVAE_REQUIRE(pd_images_ok(images_per_block), "pixel_decode: %d images per workgroup are not built (1, 2 or 4 only)", images_per_block);
   EVAE_REQUIRE(table && table_len == kPdHeader + PD_SLOTS, "pixel_decode: the offset table must hold %d entries", kPdHeader + PD_SLOTS);
   EVAE_REQUIRE(table[0] == kPdMagic, "pixel_decode: not a packed-weight table");
   EVAE_REQUIRE(table[1] == kPdC && table[2] == kPdC, "pixel_decode: channel counts %d / %d are not supported (%d only)", table[1],
@@ -525,15 +563,17 @@ extern "C" int evae_pixel_decode(const float* packed, const int* table, int tabl
   if (B == 0 || t0 == t1) return EVAE_OK;
   EVAE_REQUIRE(packed && latent && x && mean && cache && (((uintptr_t)packed | (uintptr_t)cache) & 15) == 0,
                "pixel_decode: null or unaligned pointer");
-  p.w = packed; p.latent = latent; p.x = x; p.u = u; p.mean = mean; p.cache = cache;
+  p.w = packed; p.latent = latent; p.x = x; p.u = u; p.start = u != nullptr ? start : nullptr; p.mean = mean; p.cache = cache;
   p.B = B; p.t0 = t0; p.t1 = t1;
-  const size_t lds = evae_pixel_decode_lds_bytes();
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)pixel_decode_kernel<kPdImages>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr = true;
+  switch (images_per_block) {
+    case 1: pd_launch<1>(p, (hipStream_t)s); break;
+    case 2: pd_launch<2>(p, (hipStream_t)s); break;
+    default: pd_launch<4>(p, (hipStream_t)s); break;
   }
-  const int blocks = (B + kPdImages - 1) / kPdImages;
-  pixel_decode_kernel<kPdImages><<<blocks, kPdThreads, lds, (hipStream_t)s>>>(p);
   return check_launch("pixel_decode");
+}
+
+extern "C" int evae_pixel_decode(const float* packed, const int* table, int table_len, const float* latent, float* x, const float* u,
+                                 float* mean, float* cache, int B, int t0, int t1, evae_stream_t s) {
+  return evae_pixel_decode_ex(packed, table, table_len, latent, x, u, nullptr, mean, cache, B, t0, t1, kPdImages, s);
 }

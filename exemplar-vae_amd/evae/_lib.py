@@ -181,6 +181,9 @@ SIGNATURES = {
     "evae_pixel_decode_lds_bytes": (_z, []),
     "evae_pixel_decode_slot_floats": (_i, [_i]),
     "evae_pixel_decode": (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
+    "evae_pixel_decode_lds_bytes_for": (_z, [_i]),
+    "evae_pixel_decode_choose_images": (_i, [_i]),
+    "evae_pixel_decode_ex": (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "evae_elu_dropout_fwd": (_i, [_p, _z, _f, _q, _q, _p, _p]),
     "evae_elu_dropout_bwd": (_i, [_p, _p, _z, _f, _q, _q, _p, _p]),
     "evae_dropout_step_offset": (_q, [_q, _u]),

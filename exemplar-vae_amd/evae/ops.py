@@ -2693,6 +2693,13 @@ class PixelDecodeCache:
         self.planes = torch.zeros((B, int(_lib.load().evae_pixel_decode_cache_floats())), device=device)
         self.mean = torch.zeros((B, 784), device=device)
 
+    def rows(self, n, mean=None):
+        """the cache of this one's first n images as a view, its means kept in `mean` [n, 784] when that is given: a launch over
+        [0, t1) reads what it wrote itself (pixel t reads positions < t), so the planes of one finished batch serve the next"""
+        view = PixelDecodeCache.__new__(PixelDecodeCache)
+        view.planes, view.mean = self.planes[:n], self.mean[:n] if mean is None else mean
+        return view
+
 
 def pixel_decode_pack(pixelsnail, mean_head):
     """PixelSNAIL module + the mean head (models/PixelCNN.py: self.pixelcnn, self.p_x_mean) -> PixelDecodeWeights, once per generation:
@@ -2742,13 +2749,27 @@ def pixel_decode_pack(pixelsnail, mean_head):
         return PixelDecodeWeights(buf, lay["table"], lay["entries"])
 
 
-def pixel_decode(packed, latent, x, u=None, t0=0, t1=784, cache=None):
+def pixel_decode_choose_images(B):
+    """images per workgroup the library picks for a launch of B images (evae_pixel_decode_choose_images: host arithmetic)"""
+    return int(_lib.load().evae_pixel_decode_choose_images(int(B)))
+
+
+def pixel_decode_cache_bytes(B):
+    """device bytes of the PixelDecodeCache of B images: its planes and its means"""
+    return int(B) * 4 * (int(_lib.load().evae_pixel_decode_cache_floats()) + 784)
+
+
+def pixel_decode(packed, latent, x, u=None, t0=0, t1=784, cache=None, start=None, images_per_block=None):
     """The eval-mode pixelcnn decoder at the pixels t0 <= t < t1 in raster order, one launch (csrc/evae_pixel_decode.hip).
     packed: pixel_decode_pack(...); latent [B, 2, 28, 28]; x [B, 784] float32; u [B, 784] uniforms or None; cache: the
     PixelDecodeCache of earlier launches over the same images (None: a fresh one, for t0 = 0).
     Returns (mean, x, cache): mean = cache.mean [B, 784], written at the pixels of every launch so far.  With u, x[:, t] is set IN
     PLACE to (u[:, t] < mean[:, t]) before pixel t + 1 is evaluated (x must then be a contiguous float32 tensor); without u the
-    call is teacher-forced and x is only read.  No gradients: raises if an input requires grad while grad is enabled."""
+    call is teacher-forced and x is only read.  No gradients: raises if an input requires grad while grad is enabled.
+    start: with u, image b keeps x[b, :start[b]] as given and is drawn from pixel start[b] on (<= 0: all of it, >= 784: none of
+    it; the means are written either way) -- an int32 or int64 device tensor [B], or an int for the whole batch; None: 0.  Without u
+    it is ignored.  images_per_block: 1, 2 or 4 images to a workgroup, None: the build's default, 'auto':
+    pixel_decode_choose_images(B).  The cache does not depend on it; the means do, at rounding level."""
     lib = _lib.load()
     ts = (packed.buffer, latent, x, u)
     _need_cuda(*ts)
@@ -2764,11 +2785,33 @@ def pixel_decode(packed, latent, x, u=None, t0=0, t1=784, cache=None):
     else:
         x = _f32(x)
     latent = _f32(latent)
+    if start is not None:
+        if isinstance(start, torch.Tensor):
+            if start.device != x.device or tuple(start.shape) != (B,) or start.dtype not in (torch.int32, torch.int64):
+                raise _lib.EvaeError("pixel_decode: start must be an int32 or int64 tensor [%d] on %s (got %s %s on %s)"
+                                     % (B, x.device, start.dtype, tuple(start.shape), start.device))
+            if start.dtype != torch.int32:
+                start = start.clamp(-1, 784).to(torch.int32)                     # (outside [0, 784] only the side matters)
+            start = start.contiguous()
+        else:
+            start = torch.full((B,), min(max(int(start), -1), 784), dtype=torch.int32, device=x.device)
+    if images_per_block is None:
+        G = int(lib.evae_pixel_decode_images_per_block())
+    elif isinstance(images_per_block, str):
+        if images_per_block != 'auto':
+            raise _lib.EvaeError("pixel_decode: images_per_block must be 1, 2, 4, None or 'auto' (got %r)" % (images_per_block,))
+        G = int(lib.evae_pixel_decode_choose_images(B))
+    else:
+        G = int(images_per_block)
     if cache is None:
         cache = PixelDecodeCache(B, x.device)
     if cache.mean.shape[0] != B or cache.planes.shape[0] != B:
         raise _lib.EvaeError("pixel_decode: the cache was made for %d images, not %d" % (cache.mean.shape[0], B))
     table = (C.c_int * len(packed.table))(*packed.table)
-    _lib.check(lib.evae_pixel_decode(_p(packed.buffer), table, len(packed.table), _p(latent), _p(x), _p(u), _p(cache.mean), _p(cache.planes),
-                                     B, int(t0), int(t1), _stream()), "evae_pixel_decode")
+    if start is None and images_per_block is None:
+        _lib.check(lib.evae_pixel_decode(_p(packed.buffer), table, len(packed.table), _p(latent), _p(x), _p(u), _p(cache.mean),
+                                         _p(cache.planes), B, int(t0), int(t1), _stream()), "evae_pixel_decode")
+    else:
+        _lib.check(lib.evae_pixel_decode_ex(_p(packed.buffer), table, len(packed.table), _p(latent), _p(x), _p(u), _p(start),
+                                            _p(cache.mean), _p(cache.planes), B, int(t0), int(t1), G, _stream()), "evae_pixel_decode_ex")
     return cache.mean, x, cache

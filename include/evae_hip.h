@@ -590,6 +590,24 @@ size_t evae_pixel_decode_lds_bytes(void);
 int evae_pixel_decode_slot_floats(int slot);
 int evae_pixel_decode(const float* packed, const int* table, int table_len, const float* latent, float* x, const float* u, float* mean,
                       float* cache, int B, int t0, int t1, evae_stream_t stream);
+/* The same launch with two more choices.  The library holds the kernel for 1, 2 and 4 images per workgroup (more images amortise
+ * the weight stream over a workgroup's images but lengthen every phase; past 256 images, one per CU, the workgroups of 1 queue in
+ * rounds); evae_pixel_decode_images_per_block() is the build's default and what evae_pixel_decode launches.
+ *   images_per_block  1, 2 or 4; anything else is EVAE_EINVAL before any launch, with the value in the message.  The cache layout
+ *            of an image does not depend on it: a cache begun at one value may be continued at another.  Results at one value are
+ *            bit-identical from run to run; across values the means differ at rounding level (the attention deals
+ *            256 / (8 images_per_block) lanes to a head, so the order of its sum changes).
+ *   start    device int32 [B] or NULL (= all zeros), read only when u is given: pixel t of image b is drawn, and x[b, t] written,
+ *            only when t >= start[b]; for t < start[b] the kernel reads x[b, t] as given and leaves it.  mean[b, t] is written
+ *            either way.  start[b] <= 0 samples the whole image, start[b] >= 784 teacher-forces it.  Without u, start is ignored.
+ * evae_pixel_decode(...) == evae_pixel_decode_ex(..., start = NULL, images_per_block = the default), bit for bit.
+ * evae_pixel_decode_lds_bytes_for(g): dynamic LDS of the instance for g images, 0 for a g that is not built.
+ * evae_pixel_decode_choose_images(B): the images per workgroup the library picks for B images (host arithmetic; 1 up to 256). */
+size_t evae_pixel_decode_lds_bytes_for(int g);
+int evae_pixel_decode_choose_images(int B);
+int evae_pixel_decode_ex(const float* packed, const int* table, int table_len, const float* latent, float* x, const float* u,
+                         const int* start, float* mean, float* cache, int B, int t0, int t1, int images_per_block,
+                         evae_stream_t stream);
 
 /* Window convolutions over pre-split pixel images (csrc/evae_conv_win.h): the gated layers BETWEEN two layers of a convolutional
  * encoder stack (reference utils/nn.py:72-97, models/convHVAE_2level.py:21-46), whose activations then never exist as fp32
