@@ -723,7 +723,7 @@ static int launch_prior_mfma(const float* z, int B, const float* centres, int C,
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(NT) void prior_merge_kernel(const float* __restrict__ pm,
                                                          const float* __restrict__ ps,
-                                                         const float* __restrict__ pn, int R, int B,
+                                                         const float* __restrict__ pn, int R, int ldp, int B,
                                                          int finalize, float c_total,
                                                          float* __restrict__ o0, float* __restrict__ o1,
                                                          float* __restrict__ o2) {
@@ -731,14 +731,14 @@ __global__ __launch_bounds__(NT) void prior_merge_kernel(const float* __restrict
   const int row = blockIdx.x * (NT / 64) + (threadIdx.x >> 6);
   if (row >= B) return;
   float m = -INFINITY;
-  for (int r = lane; r < R; r += 64) m = fmaxf(m, pm[(size_t)r * B + row]);
+  for (int r = lane; r < R; r += 64) m = fmaxf(m, pm[(size_t)r * ldp + row]);
   m = wave_max(m);
   float s = 0.f, n = 0.f;
   for (int r = lane; r < R; r += 64) {
-    float mr = pm[(size_t)r * B + row];
-    float sr = ps[(size_t)r * B + row];
+    float mr = pm[(size_t)r * ldp + row];
+    float sr = ps[(size_t)r * ldp + row];
     if (mr != -INFINITY) s += sr * expf(mr - m);
-    n += pn[(size_t)r * B + row];
+    n += pn[(size_t)r * ldp + row];
   }
   s = wave_sum(s);
   n = wave_sum(n);
@@ -1540,7 +1540,7 @@ static int prior_lse_fwd_core(const float* z, int B, const float* centres, int C
       *splits_out = ns2 | (ns << 16);
       return EVAE_OK;
     }
-    prior_merge_kernel<<<cdiv(B, NT / 64), NT, 0, stream>>>(pm, ps, pn, ns2, B, 0, 0.f, out_max, out_sumexp, out_nmask);
+    prior_merge_kernel<<<cdiv(B, NT / 64), NT, 0, stream>>>(pm, ps, pn, ns2, B, B, 0, 0.f, out_max, out_sumexp, out_nmask);
     return check_launch("prior_merge_kernel(splits)");
   }
   size_t lds = prior_lds_bytes(g, false);
@@ -1565,7 +1565,7 @@ static int prior_lse_fwd_core(const float* z, int B, const float* centres, int C
   int rc = check_launch("prior_fwd_kernel");
   if (rc) return rc;
   if (splits_out) { *splits_out = ns | (ns << 16); return EVAE_OK; }
-  prior_merge_kernel<<<cdiv(B, NT / 64), NT, 0, stream>>>(pm, ps, pn, ns, B, 0, 0.f, out_max, out_sumexp,
+  prior_merge_kernel<<<cdiv(B, NT / 64), NT, 0, stream>>>(pm, ps, pn, ns, B, B, 0, 0.f, out_max, out_sumexp,
                                                         out_nmask);
   return check_launch("prior_merge_kernel(splits)");
 }
@@ -1653,9 +1653,22 @@ extern "C" int evae_prior_merge(const float* max, const float* sumexp, const flo
   EVAE_REQUIRE(R >= 1 && B >= 0, "prior_merge: bad sizes R=%d B=%d", R, B);
   if (B == 0) return EVAE_OK;
   EVAE_REQUIRE(max && sumexp && nmask && out_logprior, "prior_merge: null pointer");
-  prior_merge_kernel<<<cdiv(B, NT / 64), NT, 0, stream>>>(max, sumexp, nmask, R, B, 1, c_total,
+  prior_merge_kernel<<<cdiv(B, NT / 64), NT, 0, stream>>>(max, sumexp, nmask, R, B, B, 1, c_total,
                                                         out_logprior, out_lse, nullptr);
   return check_launch("prior_merge_kernel");
+}
+
+// The same merge over B columns of wider partial rows (row stride ldp >= B): a rank of a data-parallel step merges its own B
+// queries straight out of the all-gathered [R x R B] buffer (evae/shard.py::ShardedPriorLogPBatch).
+extern "C" int evae_prior_merge_ld(const float* max, const float* sumexp, const float* nmask, int R, int ldp, int B,
+                                   float c_total, float* out_logprior, float* out_lse, evae_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  EVAE_REQUIRE(R >= 1 && B >= 0 && ldp >= B, "prior_merge_ld: bad sizes R=%d B=%d ldp=%d", R, B, ldp);
+  if (B == 0) return EVAE_OK;
+  EVAE_REQUIRE(max && sumexp && nmask && out_logprior, "prior_merge_ld: null pointer");
+  prior_merge_kernel<<<cdiv(B, NT / 64), NT, 0, stream>>>(max, sumexp, nmask, R, ldp, B, 1, c_total,
+                                                        out_logprior, out_lse, nullptr);
+  return check_launch("prior_merge_kernel(ld)");
 }
 
 extern "C" size_t evae_prior_lse_bwd_workspace_bytes(int B, int C, int zdim) {

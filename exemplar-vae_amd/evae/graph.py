@@ -201,7 +201,7 @@ class GraphedTrainStep:
         self.seed = int(torch.initial_seed())
         if model._sharded() and getattr(a, 'shard_batch', False):
             # data-parallel batches: every rank needs its own noise (replicated batches need the SAME noise on every rank)
-            self.seed += 0x9E3779B97F4A7C15 * (shard.world()[0] + 1)
+            self.seed += ops.RANK_SALT * (shard.world()[0] + 1)
         self.seed &= 0x7FFFFFFFFFFFFFFF
         # ... unless the model carries its own noise hook (an instance-level _draw_eps: tests, deterministic runs)
         own_noise = a.model_name == 'vae' and '_draw_eps' not in model.__dict__

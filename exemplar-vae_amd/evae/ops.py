@@ -200,15 +200,32 @@ def prior_merge(m, s, n, c_total, out=None):
     (csrc/evae_prior.hip::prior_merge_kernel)."""
     lib = _lib.load()
     _need_cuda(m, s, n)
-    m, s, n = _f32(m), _f32(s), _f32(n)
+    ldp = _column_block_stride(m, s, n)
+    if ldp is None:
+        m, s, n = _f32(m), _f32(s), _f32(n)
     if m.dim() == 1:
         m, s, n = m[None], s[None], n[None]
     R, B = m.shape
     lp, lse = out if out is not None else (torch.empty(B, device=m.device), torch.empty((2, B), device=m.device))
     assert lse.numel() == 2 * B and lse.is_contiguous()
+    if ldp is not None:
+        # B columns of wider rows (a rank's own queries in the all-gathered partials, evae/shard.py): merged where they lie
+        _lib.check(lib.evae_prior_merge_ld(_p(m), _p(s), _p(n), R, ldp, B, float(c_total), _p(lp), _p(lse), _stream()),
+                   "evae_prior_merge_ld")
+        return lp, lse
     _lib.check(lib.evae_prior_merge(_p(m), _p(s), _p(n), R, B, float(c_total), _p(lp), _p(lse), _stream()),
                "evae_prior_merge")
     return lp, lse
+
+
+def _column_block_stride(m, s, n):
+    """The common row stride of three fp32 [R x B] views that are column blocks of wider row-major buffers (unit column stride,
+    rows ldp > B apart) -- or None: anything else goes through the contiguous form."""
+    if not all(t.dim() == 2 and t.dtype == torch.float32 and t.shape == m.shape and t.shape[1] > 0 for t in (m, s, n)):
+        return None
+    if any(t.is_contiguous() or t.stride(1) != 1 or t.stride(0) != m.stride(0) for t in (m, s, n)):
+        return None
+    return int(m.stride(0)) if m.stride(0) > m.shape[1] else None
 
 
 _PT_STATE = {}
@@ -2389,14 +2406,30 @@ def adam_normgrad_step(params, grads, exp_avgs, exp_avg_sqs, step, lr, beta1, be
 # PixelSNAIL decoder (utils/nn.py: CausalAttention, GatedResBlock): csrc/evae_attn.hip
 # ------------------------------------------------------------------------------------------------
 _DROPOUT_CALLS = [0]
+_DROPOUT_SALT = [0]        # added to the seed of every eager mask of this process; 0: the masks of torch.manual_seed alone
+RANK_SALT = 0x9E3779B97F4A7C15      # per-rank noise: seed + RANK_SALT * (rank + 1), the fold of the captured runner (evae/graph.py)
+
+
+def dropout_salt(salt=None):
+    """The process-level salt of dropout_rng(); with an argument, set it first.  Data-parallel batches (args.shard_batch) set
+    rank_salt(rank): torch.initial_seed() has to be the same on every rank (the common exemplar draw), and ranks that hold different
+    images must not drop the same elements.  Replicated batches keep 0: their ranks need identical masks."""
+    if salt is not None:
+        _DROPOUT_SALT[0] = int(salt) & 0xFFFFFFFFFFFFFFFF
+    return _DROPOUT_SALT[0]
+
+
+def rank_salt(rank):
+    return (RANK_SALT * (int(rank) + 1)) & 0xFFFFFFFFFFFFFFFF
 
 
 def dropout_rng():
-    """(seed, offset) of the next dropout mask: the seed of torch.manual_seed, and a per-process counter that every dropout call
-    advances (it is the high half of the Philox counter, so no two calls of a process share a mask)."""
+    """(seed, offset) of the next dropout mask: the seed of torch.manual_seed (plus the process's salt, dropout_salt), and a
+    per-process counter that every dropout call advances (it is the high half of the Philox counter, so no two calls of a
+    process share a mask)."""
     off = _DROPOUT_CALLS[0]
     _DROPOUT_CALLS[0] = off + 1
-    return int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF, off
+    return (int(torch.initial_seed()) + _DROPOUT_SALT[0]) & 0xFFFFFFFFFFFFFFFF, off
 
 
 class StepRng(collections.namedtuple("StepRng", "seed_ctr ordinal")):

@@ -15,7 +15,8 @@ sum-all-reduced.  Parameter gradients are then averaged over ranks (allreduce_gr
 AdamNormGrad.step) -- dcentres is pre-scaled by R so that the average equals
 (replicated batch-path gradient) + sum_r (shard-r exemplar-path gradient), i.e. the single-GPU gradient.
 
-Data-parallel batches (args.shard_batch, evae/fused_vae.py): every rank trains on its OWN batch (global batch R*B,
+Data-parallel batches (args.shard_batch; evae/fused_vae.py for the fused `vae` node, ShardedPriorLogPBatch below for every
+configuration on the modular path): every rank trains on its OWN batch (global batch R*B,
 gradients averaged as usual) while the exemplars stay sharded.  Each rank then scores the latents of ALL ranks
 against its shard -- all-gather of z [R*B x z] (and the dataset indices for the leave-one-out mask), the same number
 of pairs as B queries against all C exemplars -- the partials are all-gathered and every rank merges its own B
@@ -175,6 +176,69 @@ class ShardedPriorLogP(torch.autograd.Function):
         dlv = packed[dz.numel():].reshape(log_var_row.shape)
         R = dist.get_world_size(group)
         return dz, dc * float(R), dlv, None, None, None, None
+
+
+# ---- data-parallel batches on the modular path (args.shard_batch; the module docstring's last paragraph) ----------------------------
+# The host side of the exchange, free of device kernels so that two gloo ranks on CPU tensors can run it (tests/test_shard_batch_gloo.py).
+# Every rank must hold the same number of rows B (the collectives gather equal blocks): loaders use drop_last.
+def gather_queries(z, zi, group=None):
+    """This rank's latents [B x z] and their dataset indices ([B] or None: no leave-one-out mask) -> those of ALL ranks in rank
+    order, ([R B x z], [R B] or None)."""
+    z_all = _all_gather_flat(z.contiguous(), group).reshape(-1, z.shape[1])
+    zi_all = None if zi is None else _all_gather_flat(zi.reshape(-1).contiguous(), group).reshape(-1)
+    return z_all, zi_all
+
+
+def own_columns(parts, B, group=None):
+    """The gathered partials ([R x R B] each: row r = shard r's partials of all R B queries) -> views of this rank's own B columns;
+    they are merged where they lie (ops.prior_merge reads the row stride)."""
+    r0 = dist.get_rank(group) * int(B)
+    return tuple(t[:, r0:r0 + int(B)] for t in parts)
+
+
+class ShardedPriorLogPBatch(torch.autograd.Function):
+    """log p(z_i) of THIS rank's B latents under the exemplar mixture sharded over the ranks of `group`, every rank holding its
+    own batch.  Forward: all-gather of the queries (and their dataset indices when masked), all R B of them against the local
+    shard, all-gather of the partials, merge of the own columns.  Backward: all-gather of (token, upstream gradient), the shard's
+    backward over all R B queries, sum-all-reduce of dz of which the own rows are kept.  dcentres and dlogvar leave as they are:
+    complete sums over all queries for this shard, under upstream gradients that carry 1/B where the global-batch mean carries
+    1/(R B) -- so the MEAN all-reduce of the parameter gradients (AdamNormGrad.step) makes them the global-batch gradient, like
+    every other parameter gradient of the step.  No rescaling, and no reduction of dlogvar here."""
+
+    @staticmethod
+    def forward(ctx, z, centres_local, log_var_row, z_idx, c_idx_local, c_total, group=None):
+        B = z.shape[0]
+        if z_idx is None or c_idx_local is None:
+            z_idx = c_idx_local = None
+        z_all, zi_all = gather_queries(z, z_idx, group)
+        m, s, n, _ = ops.prior_lse_fwd(z_all, centres_local, log_var_row, zi_all, c_idx_local)
+        lp, lse = ops.prior_merge(*own_columns(gather_partials(m, s, n, group), B, group), c_total)
+        ctx.save_for_backward(z_all, centres_local, log_var_row, lse)
+        ctx.misc = (zi_all, c_idx_local, group, B)
+        return lp
+
+    @staticmethod
+    def backward(ctx, g):
+        z_all, centres_local, log_var_row, lse = ctx.saved_tensors
+        zi_all, c_idx_local, group, B = ctx.misc
+        lg = _all_gather_flat(torch.cat((lse.reshape(2, B), g.reshape(1, B).to(lse.dtype))), group)         # [R x 3 x B]
+        lse_all = torch.stack((lg[:, 0].reshape(-1), lg[:, 1].reshape(-1))).contiguous()                    # token of all R B queries
+        dz_all, dc, dlv = ops.prior_lse_bwd(z_all, centres_local, log_var_row, zi_all, c_idx_local, lse_all,
+                                            lg[:, 2].reshape(-1).contiguous())
+        dist.all_reduce(dz_all, op=dist.ReduceOp.SUM, group=group)
+        r0 = dist.get_rank(group) * B
+        return dz_all[r0:r0 + B], dc, dlv.reshape(log_var_row.shape), None, None, None, None
+
+
+_NOISE_FOLDED = [False]
+
+
+def fold_rank_into_noise(group=None):
+    """Data-parallel batches: the eager dropout masks of this process (ops.dropout_rng) get the rank folded into their seed, once
+    per process -- the captured runner does the same to its own seed (evae/graph.py).  Replicated batches never call this."""
+    if not _NOISE_FOLDED[0]:
+        ops.dropout_salt(ops.rank_salt(dist.get_rank(group)))
+        _NOISE_FOLDED[0] = True
 
 
 _FLAT = [None, None]      # the flat buffer the last fused step wrote all its parameter gradients into, and the slice to reduce

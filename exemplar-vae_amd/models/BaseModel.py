@@ -187,6 +187,8 @@ class BaseModel(nn.Module, ABC):
             return self._calculate_loss_fused(x, x_indices, beta, dataset, average, cache)
         if self._fused_std_config() and self.training and x.is_cuda and torch.is_grad_enabled():
             return self._calculate_loss_fused_std(x, beta, average)
+        if self.training and self.args.prior == 'exemplar_prior' and self._data_parallel():
+            self._data_parallel_step()
         x_flat = x.reshape(x.shape[0], -1) if x.dim() != 2 else x
         if self._decoder_beside_prior(x, exemplars_embedding, dataset):
             # The decoder p(x | z) and the reconstruction term need z and nothing of the prior; the prior's exemplar set (top-k over the
@@ -273,6 +275,19 @@ class BaseModel(nn.Module, ABC):
     def _sharded(self):
         return bool(getattr(self.args, 'shard_exemplars', False)) and shard.is_active()
 
+    def _data_parallel(self):
+        """args.shard_batch in an active group: every rank trains on its own batch, the exemplars stay sharded"""
+        return bool(getattr(self.args, 'shard_batch', False)) and self._sharded()
+
+    def _data_parallel_step(self):
+        """What a training step on the modular path settles before its first launch when the ranks hold different batches: the
+        approximate prior is refused (shard.sharded_topk merges candidate lists as if every rank held the same query rows) --
+        before any collective, so no rank is left waiting for another --, and the eager dropout masks get the rank in their seed."""
+        if self.args.approximate_prior:
+            raise ValueError("approximate_prior=True cannot be combined with shard_batch=True: the sharded top-k merges the ranks' "
+                             "candidate lists for one common set of query rows; use the exact exemplar prior, or shard_exemplars alone")
+        shard.fold_rank_into_noise()
+
     def log_p_z_exemplar(self, z, z_indices, exemplars_embedding, test):
         """[B x C] matrix of log N(z_i | c_j, exp(logvar)) - log(C - #masked_i), -inf on leave-one-out hits
         (reference :98-109).  Kept for API parity (log_p_z(sum=False)) -- the loss path uses the fused kernel in log_p_z.
@@ -333,6 +348,9 @@ class BaseModel(nn.Module, ABC):
         ci = center_indices.to(z.device).reshape(-1) if masked else None
         emb_sharded = getattr(exemplars_embedding, 'sharded_total', None)
         if emb_sharded is not None:
+            if not test and getattr(self.args, 'shard_batch', False) and shard.is_active():
+                # every rank holds its own batch (args.shard_batch): the queries of all ranks meet this rank's shard
+                return shard.ShardedPriorLogPBatch.apply(z, centers, lv_row, zi, ci, emb_sharded)
             return shard.ShardedPriorLogP.apply(z, centers, lv_row, zi, ci, emb_sharded)
         return ops.prior_logp(z, centers, lv_row, zi, ci)
 

@@ -101,6 +101,10 @@ int evae_prior_merge(const float* max /* [R x B] */, const float* sumexp, const 
                      int R, int B, float c_total,
                      float* out_logprior /* [B] */, float* out_lse /* token [2 B] or NULL */,
                      evae_stream_t stream);
+/* evae_prior_merge over B columns of partial rows that are ldp >= B floats apart: a rank of a data-parallel step (every rank
+ * its own batch, exemplars sharded) merges its own B queries out of the all-gathered [R x R B] partials where they lie. */
+int evae_prior_merge_ld(const float* max, const float* sumexp, const float* nmask, int R, int ldp, int B, float c_total,
+                        float* out_logprior /* [B] */, float* out_lse /* token [2 B] or NULL */, evae_stream_t stream);
 /* The same forward, but the per-split partials of the launch stay in the workspace un-merged: three planes of
  * *plane_rows x B floats at ws, ws + plane_rows B, ws + 2 plane_rows B (max, sumexp, nmask), of which the first *nsplit
  * rows are valid (both are host integers, fixed by (B, C, zdim)).  For callers that merge them together with something
