@@ -248,6 +248,11 @@ SIGNATURES = {
     "evae_adam_normgrad_workspace_bytes": (_z, [_i]),
     "evae_adam_normgrad_step": (_i, [_p, _i, _l, _i, _d, _d, _d, _d, _d, _p, _p, _z, _p]),
     "evae_adam_normgrad_step_stats": (_i, [_p, _i, _l, _i, _d, _d, _d, _d, _d, _p, _p, _z, _p, _p, _p, _p, _p, _p, _p]),
+    "evae_tsne_max_points": (_i, []),
+    "evae_tsne_affinities": (_i, [_p, _i, _d, _i, _p, _p, _p]),
+    "evae_tsne_forces": (_i, [_p, _p, _i, _d, _i, _p, _p]),
+    "evae_tsne_update": (_i, [_p, _i, _i, _d, _d, _p, _p, _p, _p, _p, _p]),
+    "evae_tsne_stats": (_i, [_p, _i, _i, _p, _p]),
 }
 
 _lib = None

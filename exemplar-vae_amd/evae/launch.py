@@ -163,6 +163,22 @@ class Launcher:
             else:
                 call()
 
+    # exact t-SNE (csrc/evae_tsne.hip): no workspaces, every buffer is the caller's
+
+    def tsne_affinities(self, d2, N, perplexity, steps, beta, P):
+        """d2 [N x N] squared distances -> beta [N], joint P [N x N] (P may be d2): the row search and the symmetrising launch"""
+        _lib.check(self.lib.evae_tsne_affinities(vp(d2), N, float(perplexity), int(steps), vp(beta), vp(P), self.st), "tsne_affinities")
+
+    def tsne_forces(self, P, Y, N, exaggeration, want_kl, part):
+        _lib.check(self.lib.evae_tsne_forces(vp(P), vp(Y), N, float(exaggeration), int(bool(want_kl)), vp(part), self.st), "tsne_forces")
+
+    def tsne_update(self, part, N, want_kl, momentum, lr, Y, velocity, gains, grad, stats):
+        _lib.check(self.lib.evae_tsne_update(vp(part), N, int(bool(want_kl)), float(momentum), float(lr), vp(Y), vp(velocity),
+                                             vp(gains), vp(grad), vp(stats), self.st), "tsne_update")
+
+    def tsne_stats(self, part, N, want_kl, stats):
+        _lib.check(self.lib.evae_tsne_stats(vp(part), N, int(bool(want_kl)), vp(stats), self.st), "tsne_stats")
+
     def bwd_weight_group(self, jobs):
         """ONE launch for up to six thin weight gradients (evae_dense_bwd_weight_group; jobs as wgrad_jobs takes them)"""
         arr, n, _keep = wgrad_jobs(jobs)

@@ -588,6 +588,84 @@ def topk_merge(val, idx):
 
 
 # ------------------------------------------------------------------------------------------------
+# exact t-SNE (csrc/evae_tsne.hip); the driver is evae/tsne.py
+# ------------------------------------------------------------------------------------------------
+TSNE_SEARCH_STEPS = 100     # length of the precision search of every row (fixed: no data-dependent exit)
+TSNE_PART_COLS = 8          # evae_tsne_forces' row record: A_x, A_y, R_x, R_y, Z_i, K_i, S_i, unused (include/evae_hip.h)
+
+
+def tsne_max_points():
+    """largest N the t-SNE kernels take (a row of distances in one workgroup's LDS)"""
+    return int(_lib.load().evae_tsne_max_points())
+
+
+def _tsne_state(name, t, N):
+    if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (N, 2):
+        raise _lib.EvaeError("tsne: %s must be a contiguous float32 [%d x 2] tensor (it is updated in place)" % (name, N))
+
+
+def tsne_affinities(z, perplexity, steps=TSNE_SEARCH_STEPS):
+    """z [N x zd] -> (P [N x N] joint affinities: symmetric bit for bit, zero diagonal, sum 1; beta [N] row precisions).
+    The squared distances come from pairwise_distance; the conditionals and then P overwrite them in place."""
+    _need_cuda(z)
+    z = _f32(z)
+    if z.dim() != 2:
+        raise _lib.EvaeError("tsne_affinities: a [N x zd] tensor expected, got %s" % (tuple(z.shape),))
+    N = z.shape[0]
+    if N > tsne_max_points():
+        raise _lib.EvaeError("tsne_affinities: N=%d above the cap of %d points" % (N, tsne_max_points()))
+    P = pairwise_distance(z, z)
+    beta = torch.empty(N, device=z.device)
+    launch.Launcher(z.device).tsne_affinities(P, N, perplexity, steps, beta, P)
+    return P, beta
+
+
+def tsne_forces(P, Y, exaggeration=1.0, want_kl=False):
+    """One pass over the pairs at embedding Y [N x 2] -> part [N x 8] float64, row i = (A_ix, A_iy, R_ix, R_iy, Z_i, K_i, S_i, -):
+    w_ij = 1 / (1 + |y_i - y_j|^2), A_i = exaggeration sum_j P_ij w_ij (y_i - y_j), R_i = sum_j w_ij^2 (y_i - y_j),
+    Z_i = sum_{j != i} w_ij; with want_kl K_i = sum_j P_ij log(P_ij / w_ij) and S_i = sum_j P_ij (otherwise 0)."""
+    _need_cuda(P, Y)
+    N = Y.shape[0]
+    _tsne_state("Y", Y, N)
+    if P.dtype != torch.float32 or not P.is_contiguous() or tuple(P.shape) != (N, N):
+        raise _lib.EvaeError("tsne_forces: P must be a contiguous float32 [%d x %d] tensor" % (N, N))
+    part = torch.empty((N, TSNE_PART_COLS), dtype=torch.float64, device=Y.device)
+    launch.Launcher(Y.device).tsne_forces(P, Y, N, exaggeration, want_kl, part)
+    return part
+
+
+def tsne_update(part, Y, velocity, gains, momentum, lr, want_kl=False, want_grad=False):
+    """One descent step from tsne_forces' part, IN PLACE on Y, velocity, gains [N x 2]: grad = 4 (A - R / Z), scikit-learn's
+    gains (+0.2 where grad and velocity disagree in sign, x0.8 where they agree, floor 0.01), velocity = momentum velocity -
+    lr gains grad, Y += velocity, Y -= mean(Y).  -> (grad [N x 2] or None, stats float64 [2] = (Z, KL of the Y the forces were
+    taken at; 0 without want_kl))."""
+    _need_cuda(part, Y, velocity, gains)
+    N = Y.shape[0]
+    for name, t in (("Y", Y), ("velocity", velocity), ("gains", gains)):
+        _tsne_state(name, t, N)
+    _tsne_part(part, N)
+    grad = torch.empty((N, 2), device=Y.device) if want_grad else None
+    stats = torch.empty(2, dtype=torch.float64, device=Y.device)
+    launch.Launcher(Y.device).tsne_update(part, N, want_kl, momentum, lr, Y, velocity, gains, grad, stats)
+    return grad, stats
+
+
+def tsne_stats(part, want_kl=True):
+    """float64 [2] = (Z, KL) of tsne_forces' part alone (KL needs the part of a want_kl pass)"""
+    _need_cuda(part)
+    N = part.shape[0]
+    _tsne_part(part, N)
+    stats = torch.empty(2, dtype=torch.float64, device=part.device)
+    launch.Launcher(part.device).tsne_stats(part, N, want_kl, stats)
+    return stats
+
+
+def _tsne_part(part, N):
+    if part.dtype != torch.float64 or not part.is_contiguous() or tuple(part.shape) != (N, TSNE_PART_COLS):
+        raise _lib.EvaeError("tsne: part must be the float64 [%d x %d] tensor tsne_forces returns" % (N, TSNE_PART_COLS))
+
+
+# ------------------------------------------------------------------------------------------------
 # dense layers
 # ------------------------------------------------------------------------------------------------
 # The launches of this section go through evae/launch.py's Launcher (workspace names, entry points, the probe's names), built

@@ -915,6 +915,34 @@ int evae_adam_normgrad_step_stats(const evae_adam_tensor_t* tensors /* device */
                                   const float* step_size_dev, void* ws, size_t ws_bytes, const float* loss, const float* re,
                                   const float* kl, float* step3, float* totals3, int* toggle, evae_stream_t stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Exact t-SNE of the latent space (reference analysis.py --tsne_visualization hands the latents to scikit-learn's
+ * Barnes-Hut approximation on the host).  csrc/evae_tsne.hip; formulas and launch sequence: DESIGN 3.7.
+ * No workspace: every buffer is the caller's.  N is at most evae_tsne_max_points() (a row of distances in one
+ * workgroup's LDS).
+ *
+ * affinities: d2 [N x N] squared distances (evae_pairwise_distance) -> beta [N], the precision of every row's conditional
+ *   p(j|i) ~ exp(-beta_i d2_ij), j != i, at entropy log(perplexity), found by `steps` steps of a bracketing bisection from
+ *   beta = 1 (doubled / halved while one side is unbounded; fixed length, fp64), and the joint
+ *   P [N x N] = (p(j|i) + p(i|j)) / 2N with a zero diagonal, bit-equal to its transpose.  P may be d2 (in place).
+ * forces: part [N x 8] doubles, row i = { A_ix, A_iy, R_ix, R_iy, Z_i, K_i, S_i, unused } with w_ij = 1 / (1 + |y_i - y_j|^2),
+ *   A_i = exaggeration * sum_j P_ij w_ij (y_i - y_j), R_i = sum_j w_ij^2 (y_i - y_j), Z_i = sum_{j != i} w_ij and, when
+ *   want_kl, K_i = sum_j P_ij log(P_ij / w_ij), S_i = sum_j P_ij (else both 0).  Fixed summation order, no atomics.
+ * update: Z = sum_i Z_i; grad_i = 4 (A_i - R_i / Z); gains += 0.2 where grad * velocity < 0, *= 0.8 elsewhere, floor 0.01;
+ *   velocity = momentum * velocity - lr * gains * grad; Y += velocity; Y -= mean(Y).  One workgroup.  grad [N x 2] (may be
+ *   NULL) receives the gradient, stats (may be NULL) { Z, KL = sum_i K_i + log Z sum_i S_i (want_kl, else 0) }.
+ * stats: the two numbers of `stats` alone.
+ */
+int evae_tsne_max_points(void);
+int evae_tsne_affinities(const float* d2 /* [N x N] */, int N, double perplexity, int steps, float* beta /* [N] */,
+                         float* P /* [N x N], may be d2 */, evae_stream_t stream);
+int evae_tsne_forces(const float* P /* [N x N] */, const float* Y /* [N x 2] */, int N, double exaggeration, int want_kl,
+                     double* part /* [N x 8] */, evae_stream_t stream);
+int evae_tsne_update(const double* part /* [N x 8] */, int N, int want_kl, double momentum, double lr, float* Y /* [N x 2] */,
+                     float* velocity /* [N x 2] */, float* gains /* [N x 2] */, float* grad /* [N x 2] or NULL */,
+                     double* stats /* [2] or NULL */, evae_stream_t stream);
+int evae_tsne_stats(const double* part /* [N x 8] */, int N, int want_kl, double* stats /* [2] */, evae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
