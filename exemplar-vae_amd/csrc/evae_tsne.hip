@@ -13,7 +13,8 @@
 //               combined across lanes and waves in a fixed order -- no atomics.
 //   update:     ONE workgroup: Z (and KL) as fixed-order fp64 sums over the rows, gradient, scikit-learn's gains / velocity
 //               update, the re-centring of Y.  It needs Z of every row, hence the second launch of an iteration; there is no
-//               grid-wide barrier anywhere in this file.
+//               grid-wide barrier anywhere in this file.  evae_tsne_nn.hip (sparse P, N above the cap below) ends its iteration
+//               with this launch too.
 #include "evae_common.h"
 
 namespace evae {
@@ -306,9 +307,10 @@ extern "C" int evae_tsne_forces(const float* P, const float* Y, int N, double ex
   return check_launch("tsne_forces_kernel");
 }
 
+// update and stats serve the sparse path too (evae_tsne_nn.hip): one workgroup strides over any N, so their bound is that path's
 extern "C" int evae_tsne_update(const double* part, int N, int want_kl, double momentum, double lr, float* Y, float* velocity,
                                 float* gains, float* grad, double* stats, evae_stream_t stream_) {
-  EVAE_REQUIRE(N >= 2 && N <= kTsneMaxPoints, "tsne_update: N=%d outside [2, %d]", N, kTsneMaxPoints);
+  EVAE_REQUIRE(N >= 2 && N <= evae_tsne_nn_max_points(), "tsne_update: N=%d outside [2, %d]", N, evae_tsne_nn_max_points());
   EVAE_REQUIRE(part && Y && velocity && gains, "tsne_update: null pointer");
   tsne_update_kernel<<<1, kUpdateThreads, 0, (hipStream_t)stream_>>>(part, N, want_kl, momentum, lr, Y, velocity, gains, grad,
                                                                     stats);
@@ -316,7 +318,7 @@ extern "C" int evae_tsne_update(const double* part, int N, int want_kl, double m
 }
 
 extern "C" int evae_tsne_stats(const double* part, int N, int want_kl, double* stats, evae_stream_t stream_) {
-  EVAE_REQUIRE(N >= 2 && N <= kTsneMaxPoints, "tsne_stats: N=%d outside [2, %d]", N, kTsneMaxPoints);
+  EVAE_REQUIRE(N >= 2 && N <= evae_tsne_nn_max_points(), "tsne_stats: N=%d outside [2, %d]", N, evae_tsne_nn_max_points());
   EVAE_REQUIRE(part && stats, "tsne_stats: null pointer");
   tsne_update_kernel<<<1, kUpdateThreads, 0, (hipStream_t)stream_>>>(part, N, want_kl, 0.0, 0.0, nullptr, nullptr, nullptr,
                                                                     nullptr, stats);

@@ -253,6 +253,14 @@ SIGNATURES = {
     "evae_tsne_forces": (_i, [_p, _p, _i, _d, _i, _p, _p]),
     "evae_tsne_update": (_i, [_p, _i, _i, _d, _d, _p, _p, _p, _p, _p, _p]),
     "evae_tsne_stats": (_i, [_p, _i, _i, _p, _p]),
+    "evae_tsne_nn_max_points": (_i, []),
+    "evae_tsne_nn_max_neighbours": (_i, []),
+    "evae_tsne_knn_workspace_bytes": (_z, [_i, _i]),
+    "evae_tsne_knn": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _z, _p]),
+    "evae_tsne_nn_conditionals": (_i, [_p, _i, _i, _d, _i, _p, _p, _p]),
+    "evae_tsne_nn_joint": (_i, [_p, _l, _p, _p, _i, _i, _p, _p]),
+    "evae_tsne_nn_forces_workspace_bytes": (_z, [_i]),
+    "evae_tsne_nn_forces": (_i, [_p, _p, _p, _p, _i, _d, _i, _p, _p, _z, _p]),
 }
 
 _lib = None

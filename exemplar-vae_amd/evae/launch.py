@@ -179,6 +179,21 @@ class Launcher:
     def tsne_stats(self, part, N, want_kl, stats):
         _lib.check(self.lib.evae_tsne_stats(vp(part), N, int(bool(want_kl)), vp(stats), self.st), "tsne_stats")
 
+    # t-SNE on sparse affinities (csrc/evae_tsne_nn.hip): the two workspaces are the caller's too
+    def tsne_knn(self, z, N, zd, k, strip_rows, idx, d2, ws):
+        _lib.check(self.lib.evae_tsne_knn(vp(z), N, zd, int(k), int(strip_rows), vp(idx), vp(d2), vp(ws), ws.numel(), self.st), "tsne_knn")
+
+    def tsne_nn_conditionals(self, d2, N, k, perplexity, steps, beta, cond):
+        _lib.check(self.lib.evae_tsne_nn_conditionals(vp(d2), N, int(k), float(perplexity), int(steps), vp(beta), vp(cond), self.st),
+                   "tsne_nn_conditionals")
+
+    def tsne_nn_joint(self, cond, ia, ib, nnz, N, val):
+        _lib.check(self.lib.evae_tsne_nn_joint(vp(cond), cond.numel(), vp(ia), vp(ib), int(nnz), N, vp(val), self.st), "tsne_nn_joint")
+
+    def tsne_nn_forces(self, row_ptr, col, val, Y, N, exaggeration, want_kl, part, ws):
+        _lib.check(self.lib.evae_tsne_nn_forces(vp(row_ptr), vp(col), vp(val), vp(Y), N, float(exaggeration), int(bool(want_kl)),
+                                                vp(part), vp(ws), ws.numel(), self.st), "tsne_nn_forces")
+
     def bwd_weight_group(self, jobs):
         """ONE launch for up to six thin weight gradients (evae_dense_bwd_weight_group; jobs as wgrad_jobs takes them)"""
         arr, n, _keep = wgrad_jobs(jobs)

@@ -666,6 +666,122 @@ def _tsne_part(part, N):
 
 
 # ------------------------------------------------------------------------------------------------
+# t-SNE on sparse affinities with exact repulsion (csrc/evae_tsne_nn.hip); TSNE(method='neighbours')
+# ------------------------------------------------------------------------------------------------
+def tsne_nn_max_points():
+    """largest N of the sparse path (include/evae_hip.h says what sets it); tsne_update and tsne_stats take as many"""
+    return int(_lib.load().evae_tsne_nn_max_points())
+
+
+def tsne_nn_max_neighbours():
+    """largest k of tsne_knn: one wave holds a row of the precision search in registers"""
+    return int(_lib.load().evae_tsne_nn_max_neighbours())
+
+
+def tsne_nn_neighbours(N, perplexity):
+    """scikit-learn's n_neighbors: min(N - 1, floor(3 perplexity) + 1)"""
+    return min(int(N) - 1, int(3.0 * float(perplexity) + 1))
+
+
+def tsne_knn(z, k, strip_rows=0):
+    """z [N x zd] -> (idx int32 [N x k], d2 float32 [N x k]): every point's k nearest OTHER points, nearest first, ordered by
+    (value, index); fp64-accumulated squared distances as pairwise_distance gives them; the point itself is left out by index,
+    so its exact duplicates stay eligible.  strip_rows: query rows per strip of distances (0: what fits 256 MiB); the result
+    does not depend on it."""
+    _need_cuda(z)
+    z = _f32(z)
+    if z.dim() != 2:
+        raise _lib.EvaeError("tsne_knn: a [N x zd] tensor expected, got %s" % (tuple(z.shape),))
+    N, zd = z.shape
+    k, strip_rows = int(k), int(strip_rows)
+    if N > tsne_nn_max_points():
+        raise _lib.EvaeError("tsne_knn: N=%d above the cap of %d points" % (N, tsne_nn_max_points()))
+    if not 1 <= k <= min(N - 1, tsne_nn_max_neighbours()):
+        raise _lib.EvaeError("tsne_knn: k=%d outside [1, min(N - 1 = %d, %d)]" % (k, N - 1, tsne_nn_max_neighbours()))
+    if strip_rows < 0:
+        raise _lib.EvaeError("tsne_knn: strip_rows=%d (0 = automatic)" % strip_rows)
+    idx = torch.empty((N, k), dtype=torch.int32, device=z.device)
+    d2 = torch.empty((N, k), device=z.device)
+    ws = torch.empty(_lib.load().evae_tsne_knn_workspace_bytes(N, strip_rows), dtype=torch.uint8, device=z.device)
+    launch.Launcher(z.device).tsne_knn(z, N, zd, k, strip_rows, idx, d2, ws)
+    return idx, d2
+
+
+def tsne_nn_conditionals(d2, perplexity, steps=TSNE_SEARCH_STEPS):
+    """d2 [N x k] from tsne_knn -> (beta [N], cond [N x k]): the precision search of tsne_affinities over each row's k values
+    and the row's conditional p(j|i) on them (rows sum to 1)."""
+    _need_cuda(d2)
+    if d2.dim() != 2 or d2.dtype != torch.float32 or not d2.is_contiguous():
+        raise _lib.EvaeError("tsne_nn_conditionals: d2 must be a contiguous float32 [N x k] tensor")
+    N, k = d2.shape
+    beta = torch.empty(N, device=d2.device)
+    cond = torch.empty((N, k), device=d2.device)
+    launch.Launcher(d2.device).tsne_nn_conditionals(d2, N, k, perplexity, steps, beta, cond)
+    return beta, cond
+
+
+def tsne_nn_affinities(z, perplexity, steps=TSNE_SEARCH_STEPS, strip_rows=0):
+    """z [N x zd] -> (row_ptr int32 [N + 1], col int32 [nnz], val float32 [nnz], beta [N]): the joint
+    P_ij = (p(j|i) + p(i|j)) / 2N in CSR, a conditional outside its row's k = min(N - 1, floor(3 perplexity) + 1) nearest
+    neighbours being 0.  Columns ascend strictly within a row, there is no diagonal, nnz <= 2 N k, and val is bit-equal to its
+    transpose.  The pattern is index plumbing in torch (one stable sort of the int64 keys i N + j of the forward edges and
+    j N + i of the reverse ones; equal keys, two at most, end up adjacent); every floating-point value is formed in a kernel."""
+    _need_cuda(z)
+    z = _f32(z)
+    if z.dim() != 2:
+        raise _lib.EvaeError("tsne_nn_affinities: a [N x zd] tensor expected, got %s" % (tuple(z.shape),))
+    N = z.shape[0]
+    if not 0.0 < float(perplexity) < N:
+        raise _lib.EvaeError("tsne_nn_affinities: perplexity %g outside (0, N=%d)" % (perplexity, N))
+    k = tsne_nn_neighbours(N, perplexity)
+    idx, d2 = tsne_knn(z, k, strip_rows)
+    beta, cond = tsne_nn_conditionals(d2, perplexity, steps)
+    del d2
+    E = N * k
+    rows = torch.arange(N, device=z.device, dtype=torch.int64).repeat_interleave(k)
+    cols = idx.reshape(-1).long()
+    keys, perm = torch.sort(torch.cat((rows * N + cols, cols * N + rows)), stable=True)     # forward edges first among equals
+    del rows, cols, idx
+    first = torch.ones(2 * E, dtype=torch.bool, device=z.device)
+    first[1:] = keys[1:] != keys[:-1]
+    entry = torch.cumsum(first, 0) - 1                       # the CSR entry each of the 2 E edges lands in
+    nnz = int(entry[-1].item()) + 1
+    forward = perm < E
+    ia = torch.full((nnz,), -1, dtype=torch.int32, device=z.device)
+    ib = torch.full((nnz,), -1, dtype=torch.int32, device=z.device)
+    ia[entry[forward]] = perm[forward].int()                 # (i, j) listed by i: p(j|i) = cond[that edge]
+    ib[entry[~forward]] = (perm[~forward] - E).int()         # (i, j) as the reverse of j's edge to i: p(i|j) = cond[that edge]
+    keys = keys[first]
+    del perm, entry, forward, first
+    col = (keys % N).int()
+    row_ptr = torch.zeros(N + 1, dtype=torch.int32, device=z.device)
+    row_ptr[1:] = torch.cumsum(torch.bincount(keys // N, minlength=N), 0).int()
+    val = torch.empty(nnz, device=z.device)
+    launch.Launcher(z.device).tsne_nn_joint(cond, ia, ib, nnz, N, val)
+    return row_ptr, col, val, beta
+
+
+def tsne_nn_forces(row_ptr, col, val, Y, exaggeration=1.0, want_kl=False):
+    """tsne_forces on the CSR matrix of tsne_nn_affinities -> the same part [N x 8] float64: A_i, K_i, S_i over row i's
+    non-zeros, R_i and Z_i over all N points.  row_ptr [N + 1] is trusted to end at len(col) (checking would wait for the device)."""
+    _need_cuda(row_ptr, col, val, Y)
+    N = Y.shape[0]
+    _tsne_state("Y", Y, N)
+    if N > tsne_nn_max_points():
+        raise _lib.EvaeError("tsne_nn_forces: N=%d above the cap of %d points" % (N, tsne_nn_max_points()))
+    if row_ptr.dtype != torch.int32 or not row_ptr.is_contiguous() or tuple(row_ptr.shape) != (N + 1,):
+        raise _lib.EvaeError("tsne_nn_forces: row_ptr must be a contiguous int32 [%d] tensor" % (N + 1))
+    if col.dtype != torch.int32 or not col.is_contiguous() or col.dim() != 1:
+        raise _lib.EvaeError("tsne_nn_forces: col must be a contiguous int32 [nnz] tensor")
+    if val.dtype != torch.float32 or not val.is_contiguous() or tuple(val.shape) != tuple(col.shape):
+        raise _lib.EvaeError("tsne_nn_forces: val must be a contiguous float32 [%d] tensor" % col.numel())
+    part = torch.empty((N, TSNE_PART_COLS), dtype=torch.float64, device=Y.device)
+    ws = torch.empty(_lib.load().evae_tsne_nn_forces_workspace_bytes(N), dtype=torch.uint8, device=Y.device)
+    launch.Launcher(Y.device).tsne_nn_forces(row_ptr, col, val, Y, N, exaggeration, want_kl, part, ws)
+    return part
+
+
+# ------------------------------------------------------------------------------------------------
 # dense layers
 # ------------------------------------------------------------------------------------------------
 # The launches of this section go through evae/launch.py's Launcher (workspace names, entry points, the probe's names), built

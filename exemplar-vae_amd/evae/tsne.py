@@ -11,7 +11,14 @@ squared Euclidean distance, n_components other than 2, method='barnes_hut'.
 
 The cap on N: a row of distances has to fit one workgroup's LDS during the precision search (64 B + 4 N <= 160 KiB), so
 N <= 32768 (ops.tsne_max_points()).  The dense buffers at the cap: the [N x N] float32 matrix that holds the distances, then
-the conditionals, then P, in place, 4 N^2 B = 4 GiB, plus 64 N B of per-point sums and 24 N B of descent state."""
+the conditionals, then P, in place, 4 N^2 B = 4 GiB, plus 64 N B of per-point sums and 24 N B of descent state.
+
+method='neighbours' (csrc/evae_tsne_nn.hip) lifts that cap to ops.tsne_nn_max_points(): scikit-learn's large-N
+formulation without its tree.  P lives only on each point's k = min(N - 1, floor(3 perplexity) + 1) nearest neighbours (its
+_joint_probabilities_nn, symmetrised, in CSR), the attractive sum runs over those non-zeros, the repulsive sum and Z stay exact
+over all N^2 pairs (Barnes-Hut at angle 0).  No [N x N] buffer exists; k <= 256, i.e. perplexity up to 85.  The descent loop,
+learning rate, init and attributes are the same, and equal random_state still gives bit-equal embeddings.  method='exact' is
+the default and is untouched."""
 import numpy as np
 import torch
 
@@ -19,15 +26,23 @@ from . import ops
 
 EXAGGERATED_ITERS = 250      # scikit-learn's _EXPLORATION_MAX_ITER
 _INIT_STD = 1e-4
+METHODS = ('exact', 'neighbours')
 
 
 class TSNE:
     def __init__(self, n_components=2, perplexity=30.0, early_exaggeration=12.0, learning_rate='auto', n_iter=1000,
-                 random_state=None, init='random', exaggerated_iters=EXAGGERATED_ITERS, device=None):
+                 random_state=None, init='random', exaggerated_iters=EXAGGERATED_ITERS, device=None, method='exact'):
         """exaggerated_iters: how many of the n_iter iterations run with early_exaggeration and momentum 0.5 (scikit-learn
         fixes 250; short runs in tests and documents shorten it in proportion).  init: 'random' -- N(0, 1e-4^2) from a
         torch.Generator on the device seeded with random_state -- or a [N x 2] tensor / array.  device: where a host array
-        given to fit_transform goes (default cuda)."""
+        given to fit_transform goes (default cuda).  method: 'exact' (dense P, N <= ops.tsne_max_points()) or 'neighbours' (P on
+        the nearest neighbours only, repulsion still exact; N <= ops.tsne_nn_max_points(), perplexity <= 85)."""
+        if method not in METHODS:
+            raise ValueError("TSNE: method=%r; the choices are 'exact' and 'neighbours' (there is no tree: 'barnes_hut' is not "
+                             "carried over)" % (method,))
+        if method == 'neighbours' and int(3.0 * float(perplexity) + 1) > ops.tsne_nn_max_neighbours():
+            raise ValueError("TSNE: perplexity %g needs %d neighbours; method='neighbours' takes at most %d (perplexity up to 85)"
+                             % (perplexity, int(3.0 * float(perplexity) + 1), ops.tsne_nn_max_neighbours()))
         if n_components != 2:
             raise ValueError("TSNE: n_components=%r; the kernels embed in 2 dimensions only" % (n_components,))
         if not (torch.is_tensor(init) or isinstance(init, np.ndarray) or init == 'random'):
@@ -38,7 +53,7 @@ class TSNE:
             raise ValueError("TSNE: n_iter >= 1 and exaggerated_iters >= 0 expected")
         self.n_components, self.perplexity, self.early_exaggeration = 2, float(perplexity), float(early_exaggeration)
         self.learning_rate, self.n_iter, self.random_state, self.init = learning_rate, int(n_iter), random_state, init
-        self.exaggerated_iters, self.device = int(exaggerated_iters), device
+        self.exaggerated_iters, self.device, self.method = int(exaggerated_iters), device, method
         self.embedding_ = self.kl_divergence_ = self.n_iter_ = self.learning_rate_ = None
 
     def _initial(self, N, device):
@@ -63,7 +78,9 @@ class TSNE:
         N = shape[0]
         if self.perplexity >= N:
             raise ValueError("TSNE: perplexity %g must be less than the number of points %d" % (self.perplexity, N))
-        if N > ops.tsne_max_points():
+        if self.method == 'neighbours' and N > ops.tsne_nn_max_points():
+            raise ValueError("TSNE: %d points; method='neighbours' takes at most %d" % (N, ops.tsne_nn_max_points()))
+        if self.method == 'exact' and N > ops.tsne_max_points():
             raise ValueError("TSNE: %d points; the exact kernels take at most %d (a row of distances in one workgroup's LDS; "
                              "the dense matrix is 4 N^2 bytes)" % (N, ops.tsne_max_points()))
         if not torch.is_tensor(X):
@@ -74,15 +91,24 @@ class TSNE:
             lr = float(self.learning_rate)
         self.learning_rate_ = lr
         with torch.no_grad():
-            P, _ = ops.tsne_affinities(X, self.perplexity)
-            Y = self._initial(N, P.device)
+            if self.method == 'neighbours':
+                csr = ops.tsne_nn_affinities(X, self.perplexity)[:3]
+
+                def forces(Y, exaggeration, want_kl):
+                    return ops.tsne_nn_forces(*csr, Y, exaggeration, want_kl)
+            else:
+                P, _ = ops.tsne_affinities(X, self.perplexity)
+
+                def forces(Y, exaggeration, want_kl):
+                    return ops.tsne_forces(P, Y, exaggeration, want_kl)
+            Y = self._initial(N, X.device)
             velocity = torch.zeros_like(Y)
             gains = torch.ones_like(Y)
             for it in range(self.n_iter):
                 early = it < self.exaggerated_iters
-                part = ops.tsne_forces(P, Y, self.early_exaggeration if early else 1.0, False)
+                part = forces(Y, self.early_exaggeration if early else 1.0, False)
                 ops.tsne_update(part, Y, velocity, gains, 0.5 if early else 0.8, lr)
-            stats = ops.tsne_stats(ops.tsne_forces(P, Y, 1.0, True), True)
+            stats = ops.tsne_stats(forces(Y, 1.0, True), True)
         self.kl_divergence_ = float(stats[1].item())
         self.n_iter_ = self.n_iter
         self.embedding_ = Y

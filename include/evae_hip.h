@@ -919,7 +919,8 @@ int evae_adam_normgrad_step_stats(const evae_adam_tensor_t* tensors /* device */
  * Exact t-SNE of the latent space (reference analysis.py --tsne_visualization hands the latents to scikit-learn's
  * Barnes-Hut approximation on the host).  csrc/evae_tsne.hip; formulas and launch sequence: DESIGN 3.7.
  * No workspace: every buffer is the caller's.  N is at most evae_tsne_max_points() (a row of distances in one
- * workgroup's LDS).
+ * workgroup's LDS) for affinities and forces; update and stats, which the sparse path below shares, take up to
+ * evae_tsne_nn_max_points().
  *
  * affinities: d2 [N x N] squared distances (evae_pairwise_distance) -> beta [N], the precision of every row's conditional
  *   p(j|i) ~ exp(-beta_i d2_ij), j != i, at entropy log(perplexity), found by `steps` steps of a bracketing bisection from
@@ -942,6 +943,49 @@ int evae_tsne_update(const double* part /* [N x 8] */, int N, int want_kl, doubl
                      float* velocity /* [N x 2] */, float* gains /* [N x 2] */, float* grad /* [N x 2] or NULL */,
                      double* stats /* [2] or NULL */, evae_stream_t stream);
 int evae_tsne_stats(const double* part /* [N x 8] */, int N, int want_kl, double* stats /* [2] */, evae_stream_t stream);
+
+/* ----------------------------------------------------------------------------------------------
+ * t-SNE with sparse affinities and exact repulsion: scikit-learn's large-N formulation (P only on each point's
+ * k = min(N - 1, floor(3 perplexity) + 1) nearest neighbours, its _joint_probabilities_nn, symmetrised) without the tree: the
+ * repulsive sum and Z run over all N^2 pairs.  csrc/evae_tsne_nn.hip; DESIGN 3.7a.  No [N x N] buffer exists at any point.
+ * evae_tsne_update and evae_tsne_stats above serve this path too, up to evae_tsne_nn_max_points().
+ *
+ * evae_tsne_nn_max_points() = 131072.  Nothing here sits in LDS by the row, so the bound is a chosen one: N k and 2 N k (the
+ *   non-zeros) stay far inside int32 offsets at k = 256 (2^26), the automatic strip of the neighbour search is still 512 rows,
+ *   and the ONE workgroup of evae_tsne_update walks 128 rows per thread three times per iteration; beyond it that launch and the
+ *   N^2 repulsion (1.7e10 pairs an iteration at the bound) want a different design, not a larger constant.
+ * evae_tsne_nn_max_neighbours() = 256: a wave holds a row of the search in registers, 4 values per lane (perplexity up to 85).
+ *
+ * knn: z [N x zdim] -> idx [N x k] int32, d2 [N x k]: the k nearest OTHER points of every point, nearest first, order
+ *   (value ascending, index ascending).  Distances as evae_pairwise_distance gives them (direct differences accumulated in fp64,
+ *   rounded once to fp32).  The point itself is left out by index, not by distance: exact duplicates of it stay eligible.
+ *   1 <= k <= min(N - 1, 256).  The queries go in strips of strip_rows rows (0: as many as fit 256 MiB of distances); ws holds
+ *   one strip, evae_tsne_knn_workspace_bytes(N, strip_rows) bytes.  The result does not depend on strip_rows.
+ * conditionals: d2 [N x k] -> beta [N] and cond [N x k], cond[i][m] = exp(-beta_i (d2[i][m] - min_m d2[i])) / sum_m of the same,
+ *   beta_i from the search of evae_tsne_affinities over the k values: `steps` steps from beta = 1, doubled / halved while one
+ *   side is unbounded, then bisected; fp64, no data-dependent exit.
+ * joint: val[e] = (a + b) / 2N for e < nnz with a = cond[ia[e]] (0 where ia[e] < 0) and b = cond[ib[e]] likewise: the caller
+ *   pairs p(j|i) with p(i|j) for every entry (i, j) of the CSR pattern; the entry (j, i) then forms b + a, the same float.
+ * forces: the CSR matrix row_ptr [N + 1], col [nnz] (ascending within a row, no diagonal), val [nnz] and Y [N x 2] -> the part
+ *   [N x 8] record of evae_tsne_forces: A_i = exaggeration * sum over the row's non-zeros of P_ij w_ij (y_i - y_j), K_i and S_i
+ *   over the same non-zeros (want_kl, else 0), R_i and Z_i over ALL j as there (self pair left out of Z, coincident points
+ *   count with w = 1).  Two launches: the repulsion in blocks of 256 rows x a range of columns, then a wave per CSR row that also
+ *   adds the column ranges' partial sums in range order.  ws: evae_tsne_nn_forces_workspace_bytes(N) bytes of partial sums.
+ *   Fixed summation order, no floating-point atomics, no grid-wide barrier.
+ */
+int evae_tsne_nn_max_points(void);
+int evae_tsne_nn_max_neighbours(void);
+size_t evae_tsne_knn_workspace_bytes(int N, int strip_rows);
+int evae_tsne_knn(const float* z /* [N x zdim] */, int N, int zdim, int k, int strip_rows, int* idx /* [N x k] */,
+                  float* d2 /* [N x k] */, void* ws, size_t ws_bytes, evae_stream_t stream);
+int evae_tsne_nn_conditionals(const float* d2 /* [N x k] */, int N, int k, double perplexity, int steps, float* beta /* [N] */,
+                              float* cond /* [N x k] */, evae_stream_t stream);
+int evae_tsne_nn_joint(const float* cond /* [n_cond] */, int64_t n_cond, const int* ia /* [nnz] */, const int* ib /* [nnz] */,
+                       int nnz, int N, float* val /* [nnz] */, evae_stream_t stream);
+size_t evae_tsne_nn_forces_workspace_bytes(int N);
+int evae_tsne_nn_forces(const int* row_ptr /* [N + 1] */, const int* col /* [nnz] */, const float* val /* [nnz] */,
+                        const float* Y /* [N x 2] */, int N, double exaggeration, int want_kl, double* part /* [N x 8] */,
+                        void* ws, size_t ws_bytes, evae_stream_t stream);
 
 #ifdef __cplusplus
 }
