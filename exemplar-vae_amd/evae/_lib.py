@@ -261,6 +261,8 @@ SIGNATURES = {
     "evae_tsne_nn_joint": (_i, [_p, _l, _p, _p, _i, _i, _p, _p]),
     "evae_tsne_nn_forces_workspace_bytes": (_z, [_i]),
     "evae_tsne_nn_forces": (_i, [_p, _p, _p, _p, _i, _d, _i, _p, _p, _z, _p]),
+    "evae_nn_rank_workspace_bytes": (_z, [_i, _i]),
+    "evae_nn_rank": (_i, [_p, _i, _i, _p, _i, _i, _p, _p, _p, _z, _p]),
 }
 
 _lib = None

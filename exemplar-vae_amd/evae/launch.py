@@ -183,6 +183,11 @@ class Launcher:
     def tsne_knn(self, z, N, zd, k, strip_rows, idx, d2, ws):
         _lib.check(self.lib.evae_tsne_knn(vp(z), N, zd, int(k), int(strip_rows), vp(idx), vp(d2), vp(ws), ws.numel(), self.st), "tsne_knn")
 
+    def nn_rank(self, z, N, zd, nbr, k, strip_rows, rank, row_sums, ws):
+        """csrc/evae_nn_rank.hip: the strip workspace is the caller's, as tsne_knn's"""
+        _lib.check(self.lib.evae_nn_rank(vp(z), N, zd, vp(nbr), int(k), int(strip_rows), vp(rank), vp(row_sums), vp(ws), ws.numel(),
+                                         self.st), "nn_rank")
+
     def tsne_nn_conditionals(self, d2, N, k, perplexity, steps, beta, cond):
         _lib.check(self.lib.evae_tsne_nn_conditionals(vp(d2), N, int(k), float(perplexity), int(steps), vp(beta), vp(cond), self.st),
                    "tsne_nn_conditionals")

@@ -707,6 +707,34 @@ def tsne_knn(z, k, strip_rows=0):
     return idx, d2
 
 
+def nn_rank(z, nbr, strip_rows=0):
+    """z [N x zd], nbr int32 [N x k] -> (rank int32 [N x k], row_sums int64 [N x 2]) (csrc/evae_nn_rank.hip):
+    rank[i][m] = 1 + the number of points l != i with (d2(i, l), l) < (d2(i, j), j), j = nbr[i][m] -- the order and the distances
+    of tsne_knn, whose own m-th neighbour has rank m + 1.  An entry j == i or outside [0, N) gets rank 0 (nbr is trusted, not
+    checked: that would wait for the device; the kernel reads nothing for such an entry).  row_sums[i] = (sum of
+    max(0, rank - k) over the entries with rank > 0, the number of entries with 1 <= rank <= k).  Exact integers; the result does
+    not depend on strip_rows (query rows per strip of distances, 0: what fits 256 MiB)."""
+    _need_cuda(z, nbr)
+    z = _f32(z)
+    if z.dim() != 2:
+        raise _lib.EvaeError("nn_rank: a [N x zd] tensor expected, got %s" % (tuple(z.shape),))
+    N, zd = z.shape
+    if nbr.dtype != torch.int32 or not nbr.is_contiguous() or nbr.dim() != 2 or nbr.shape[0] != N:
+        raise _lib.EvaeError("nn_rank: nbr must be a contiguous int32 [%d x k] tensor" % N)
+    k, strip_rows = nbr.shape[1], int(strip_rows)
+    if not 2 <= N <= tsne_nn_max_points():
+        raise _lib.EvaeError("nn_rank: N=%d outside [2, %d]" % (N, tsne_nn_max_points()))
+    if not 1 <= k <= min(N - 1, tsne_nn_max_neighbours()):
+        raise _lib.EvaeError("nn_rank: k=%d outside [1, min(N - 1 = %d, %d)]" % (k, N - 1, tsne_nn_max_neighbours()))
+    if strip_rows < 0:
+        raise _lib.EvaeError("nn_rank: strip_rows=%d (0 = automatic)" % strip_rows)
+    rank = torch.empty((N, k), dtype=torch.int32, device=z.device)
+    row_sums = torch.empty((N, 2), dtype=torch.int64, device=z.device)
+    ws = torch.empty(_lib.load().evae_nn_rank_workspace_bytes(N, strip_rows), dtype=torch.uint8, device=z.device)
+    launch.Launcher(z.device).nn_rank(z, N, zd, nbr, k, strip_rows, rank, row_sums, ws)
+    return rank, row_sums
+
+
 def tsne_nn_conditionals(d2, perplexity, steps=TSNE_SEARCH_STEPS):
     """d2 [N x k] from tsne_knn -> (beta [N], cond [N x k]): the precision search of tsne_affinities over each row's k values
     and the row's conditional p(j|i) on them (rows sum to 1)."""

@@ -18,7 +18,11 @@ formulation without its tree.  P lives only on each point's k = min(N - 1, floor
 _joint_probabilities_nn, symmetrised, in CSR), the attractive sum runs over those non-zeros, the repulsive sum and Z stay exact
 over all N^2 pairs (Barnes-Hut at angle 0).  No [N x N] buffer exists; k <= 256, i.e. perplexity up to 85.  The descent loop,
 learning rate, init and attributes are the same, and equal random_state still gives bit-equal embeddings.  method='exact' is
-the default and is untouched."""
+the default and is untouched.
+
+trustworthiness / continuity / embedding_quality below (csrc/evae_nn_rank.hip) score an embedding against its input
+without reference to P, so the two methods -- or any later change to either -- can be compared: scikit-learn's trustworthiness,
+its mirror image and the share of preserved neighbours, exact integers from one counting pass per direction over all N^2 pairs."""
 import numpy as np
 import torch
 
@@ -117,3 +121,79 @@ class TSNE:
     def fit(self, X, y=None):
         self.fit_transform(X)
         return self
+
+
+# ------------------------------------------------------------------------------------------------
+# Quality of an embedding, independent of P (csrc/evae_nn_rank.hip): scikit-learn's trustworthiness and its mirror
+# image, as exact integers from the device.  Neither an [N x N] matrix nor a sorted row exists at any point.
+# ------------------------------------------------------------------------------------------------
+def _pair(X, X_embedded, n_neighbors, who):
+    """both spaces as float32 tensors on one device, converted as fit_transform converts its input; scikit-learn's bound on k"""
+    device = next((t.device for t in (X, X_embedded) if torch.is_tensor(t)), 'cuda')
+    out = []
+    for a in (X, X_embedded):
+        if not torch.is_tensor(a):
+            a = torch.as_tensor(np.asarray(a, dtype=np.float32), device=device)
+        if a.dim() != 2:
+            raise ValueError("%s: [N x d] inputs expected, got %s" % (who, tuple(a.shape)))
+        out.append(a)
+    N, k = out[0].shape[0], int(n_neighbors)
+    if out[1].shape[0] != N:
+        raise ValueError("%s: %d points in X, %d in X_embedded" % (who, N, out[1].shape[0]))
+    if k < 1 or k >= N / 2:
+        raise ValueError("%s: n_neighbors (%d) should be at least 1 and less than n_samples / 2 (%g)" % (who, k, N / 2))
+    return out[0], out[1], N, k
+
+
+def _rank_sums(chosen_in, ranked_in, k):
+    """the k nearest neighbours in one space, ranked in the other -> (nbr [N x k], the two integer totals of nn_rank's row sums)"""
+    with torch.no_grad():
+        nbr = ops.tsne_knn(chosen_in, k)[0]
+        totals = ops.nn_rank(ranked_in, nbr)[1].sum(dim=0).tolist()       # read once: two Python integers
+    return nbr, int(totals[0]), int(totals[1])
+
+
+def _score(penalty, N, k):
+    """scikit-learn's expression, in its order, in Python float64"""
+    return 1.0 - penalty * (2.0 / (N * k * (2.0 * N - 3.0 * k - 1.0)))
+
+
+def trustworthiness(X, X_embedded, n_neighbors=5):
+    """sklearn.manifold.trustworthiness (Venna & Kaski) under squared Euclidean distance: 1 - 2 / (N k (2N - 3k - 1)) x the sum,
+    over every point's k nearest neighbours in the embedding, of max(0, rank in X - k).  1 = no neighbour of the embedding is a
+    stranger in the input space.  Ties are ordered by index, in both spaces."""
+    X, Y, N, k = _pair(X, X_embedded, n_neighbors, "trustworthiness")
+    return _score(_rank_sums(Y, X, k)[1], N, k)
+
+
+def continuity(X, X_embedded, n_neighbors=5):
+    """trustworthiness with the two spaces swapped: the input space's neighbours, ranked in the embedding.  1 = no neighbourhood
+    of the input space is torn apart."""
+    X, Y, N, k = _pair(X, X_embedded, n_neighbors, "continuity")
+    return _score(_rank_sums(X, Y, k)[1], N, k)
+
+
+def _label_accuracy(nbr, labels):
+    """leave-one-out majority vote of every point's k neighbours' labels, ties to the lowest class: integer index plumbing"""
+    labels = torch.as_tensor(np.asarray(labels) if not torch.is_tensor(labels) else labels).to(nbr.device).reshape(-1)
+    if labels.numel() != nbr.shape[0]:
+        raise ValueError("embedding_quality: %d labels for %d points" % (labels.numel(), nbr.shape[0]))
+    classes, cls = torch.unique(labels, sorted=True, return_inverse=True)
+    C = classes.numel()
+    votes = torch.zeros((nbr.shape[0], C), dtype=torch.int64, device=nbr.device)
+    votes.scatter_add_(1, cls[nbr.long()], torch.ones(nbr.shape, dtype=torch.int64, device=nbr.device))
+    order = votes * C + (C - 1 - torch.arange(C, device=nbr.device))       # distinct within a row: most votes, then lowest class
+    return int((order.argmax(dim=1) == cls).sum().item()) / nbr.shape[0]
+
+
+def embedding_quality(X, X_embedded, n_neighbors=5, labels=None):
+    """-> dict(trustworthiness, continuity, neighbourhood_preservation, n_neighbors, n_samples[, label_accuracy]).
+    neighbourhood_preservation: the share of the k embedding-neighbours that are among the k input-neighbours too.
+    label_accuracy (with labels [N]): the share of points whose label wins the vote of their k embedding-neighbours."""
+    X, Y, N, k = _pair(X, X_embedded, n_neighbors, "embedding_quality")
+    nbr, penalty, hits = _rank_sums(Y, X, k)
+    out = dict(trustworthiness=_score(penalty, N, k), continuity=_score(_rank_sums(X, Y, k)[1], N, k),
+               neighbourhood_preservation=hits / (N * k), n_neighbors=k, n_samples=N)
+    if labels is not None:
+        out['label_accuracy'] = _label_accuracy(nbr, labels)
+    return out

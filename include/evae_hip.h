@@ -987,6 +987,29 @@ int evae_tsne_nn_forces(const int* row_ptr /* [N + 1] */, const int* col /* [nnz
                         const float* Y /* [N x 2] */, int N, double exaggeration, int want_kl, double* part /* [N x 8] */,
                         void* ws, size_t ws_bytes, evae_stream_t stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Ranks of chosen neighbours: what trustworthiness, continuity and neighbourhood preservation of an embedding are sums of
+ * (evae/tsne.py).  csrc/evae_nn_rank.hip; DESIGN 3.7b.  No [N x N] buffer exists at any point and no row is sorted.
+ *
+ * nn_rank: z [N x zdim], nbr [N x k] int32 -> rank [N x k] int32 and row_sums [N x 2] int64.  With j = nbr[i][m],
+ *   rank[i][m] = 1 + #{ l != i : (d2(i, l), l) < (d2(i, j), j) }, the comparison lexicographic (value ascending, index
+ *   ascending): the order of evae_tsne_knn, whose own m-th neighbour therefore has rank m + 1.  Distances as
+ *   evae_pairwise_distance gives them (direct differences accumulated in fp64, rounded once to fp32).  The point itself is left
+ *   out by index, not by distance: exact duplicates of it count.  An entry with j == i or j outside [0, N) gets rank 0 and adds
+ *   nothing to the sums; no distance is read for it (nbr is trusted input, as row_ptr is in evae_tsne_nn_forces: the kernel
+ *   guards instead of the host checking).  A column named twice in a row gets the same rank twice.
+ *   row_sums[i] = { sum over the entries with rank > 0 of max(0, rank - k),  #{ m : 1 <= rank[i][m] <= k } }.
+ *   1 <= k <= min(N - 1, evae_tsne_nn_max_neighbours()), N <= evae_tsne_nn_max_points().  The queries go in strips of
+ *   strip_rows rows (0: as many as fit 256 MiB of distances); ws holds one strip, evae_nn_rank_workspace_bytes(N, strip_rows)
+ *   bytes.  The result does not depend on strip_rows.  Two launches per strip: the distances, then one workgroup per row that
+ *   sorts the row's k thresholds in LDS and streams the N distances once past them.  Integer arithmetic and integer LDS atomics
+ *   only: the result is exact and the same on every run.
+ */
+size_t evae_nn_rank_workspace_bytes(int N, int strip_rows);
+int evae_nn_rank(const float* z /* [N x zdim] */, int N, int zdim, const int* nbr /* [N x k] */, int k, int strip_rows,
+                 int* rank /* [N x k] */, long long* row_sums /* [N x 2]: penalty, hits */, void* ws, size_t ws_bytes,
+                 evae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
