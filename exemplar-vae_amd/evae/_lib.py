@@ -263,6 +263,16 @@ SIGNATURES = {
     "evae_tsne_nn_forces": (_i, [_p, _p, _p, _p, _i, _d, _i, _p, _p, _z, _p]),
     "evae_nn_rank_workspace_bytes": (_z, [_i, _i]),
     "evae_nn_rank": (_i, [_p, _i, _i, _p, _i, _i, _p, _p, _p, _z, _p]),
+    "evae_pca_max_features": (_i, []),
+    "evae_pca_max_points": (_i, []),
+    "evae_pca_chunk_rows": (_i, []),
+    "evae_pca_max_sweeps": (_i, []),
+    "evae_pca_workspace_bytes": (_z, [_i, _i]),
+    "evae_pca_eigh_workspace_bytes": (_z, [_i]),
+    "evae_pca_moments": (_i, [_p, _i, _i, _p, _p, _p, _z, _p]),
+    "evae_pca_eigh": (_i, [_p, _i, _p, _p, _p, _p, _z, _p]),
+    "evae_pca_project": (_i, [_p, _i, _i, _p, _p, _i, _d, _p, _p]),
+    "evae_pca_reconstruct": (_i, [_p, _i, _i, _p, _p, _i, _p, _p]),
 }
 
 _lib = None

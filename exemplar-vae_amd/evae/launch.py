@@ -199,6 +199,21 @@ class Launcher:
         _lib.check(self.lib.evae_tsne_nn_forces(vp(row_ptr), vp(col), vp(val), vp(Y), N, float(exaggeration), int(bool(want_kl)),
                                                 vp(part), vp(ws), ws.numel(), self.st), "tsne_nn_forces")
 
+    # PCA in fp64 (csrc/evae_pca.hip): the workspaces are the caller's
+    def pca_moments(self, x, N, d, mean, cov, ws):
+        _lib.check(self.lib.evae_pca_moments(vp(x), N, d, vp(mean), vp(cov), vp(ws), ws.numel(), self.st), "pca_moments")
+
+    def pca_eigh(self, cov, d, evals, evecs, info, ws):
+        """ws: None where evae_pca_eigh_workspace_bytes(d) is 0 (the matrices sit in LDS)"""
+        _lib.check(self.lib.evae_pca_eigh(vp(cov), d, vp(evals), vp(evecs), vp(info), vp(ws), 0 if ws is None else ws.numel(),
+                                          self.st), "pca_eigh")
+
+    def pca_project(self, x, N, d, mean, W, k, scale, out):
+        _lib.check(self.lib.evae_pca_project(vp(x), N, d, vp(mean), vp(W), int(k), float(scale), vp(out), self.st), "pca_project")
+
+    def pca_reconstruct(self, y, N, k, mean, W, d, out):
+        _lib.check(self.lib.evae_pca_reconstruct(vp(y), N, int(k), vp(mean), vp(W), d, vp(out), self.st), "pca_reconstruct")
+
     def bwd_weight_group(self, jobs):
         """ONE launch for up to six thin weight gradients (evae_dense_bwd_weight_group; jobs as wgrad_jobs takes them)"""
         arr, n, _keep = wgrad_jobs(jobs)

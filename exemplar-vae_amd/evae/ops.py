@@ -810,6 +810,113 @@ def tsne_nn_forces(row_ptr, col, val, Y, exaggeration=1.0, want_kl=False):
 
 
 # ------------------------------------------------------------------------------------------------
+# PCA in fp64 (csrc/evae_pca.hip); the driver is evae/pca.py, TSNE(init='pca') its first user
+# ------------------------------------------------------------------------------------------------
+def pca_max_features():
+    """widest input the PCA kernels take (the widest latent the project has)"""
+    return int(_lib.load().evae_pca_max_features())
+
+
+def pca_max_points():
+    return int(_lib.load().evae_pca_max_points())
+
+
+def pca_chunk_rows():
+    """rows a block of pca_moments owns: the partial sums of the chunks are added in index order"""
+    return int(_lib.load().evae_pca_chunk_rows())
+
+
+def pca_max_sweeps():
+    """the compile-time bound of pca_eigh's sweep loop"""
+    return int(_lib.load().evae_pca_max_sweeps())
+
+
+def _pca_f64(name, t, shape, who):
+    if t.dtype != torch.float64 or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+        raise _lib.EvaeError("%s: %s must be a contiguous float64 %s tensor, got %s %s" % (who, name, list(shape), t.dtype,
+                                                                                          tuple(t.shape)))
+
+
+def _pca_rows(x, who):
+    _need_cuda(x)
+    x = _f32(x)
+    if x.dim() != 2:
+        raise _lib.EvaeError("%s: a [N x d] tensor expected, got %s" % (who, tuple(x.shape)))
+    if not 1 <= x.shape[1] <= pca_max_features():
+        raise _lib.EvaeError("%s: %d features outside [1, %d]" % (who, x.shape[1], pca_max_features()))
+    if not 1 <= x.shape[0] <= pca_max_points():
+        raise _lib.EvaeError("%s: N=%d outside [1, %d]" % (who, x.shape[0], pca_max_points()))
+    return x
+
+
+def pca_moments(x):
+    """x [N x d] -> (mean [d], cov [d x d]), float64: the covariance (ddof 1) of the rows centred in fp64, two passes, symmetric
+    bit for bit; equal inputs give bit-equal outputs."""
+    x = _pca_rows(x, "pca_moments")
+    N, d = x.shape
+    if N < 2:
+        raise _lib.EvaeError("pca_moments: N=%d, at least 2 rows expected" % N)
+    mean = torch.empty(d, dtype=torch.float64, device=x.device)
+    cov = torch.empty((d, d), dtype=torch.float64, device=x.device)
+    ws = torch.empty(_lib.load().evae_pca_workspace_bytes(N, d), dtype=torch.uint8, device=x.device)
+    launch.Launcher(x.device).pca_moments(x, N, d, mean, cov, ws)
+    return mean, cov
+
+
+def pca_eigh(cov):
+    """symmetric positive semi-definite cov [d x d] float64 -> (evals [d] descending, clamped at 0; evecs [d x d], row i =
+    component i, its entry of largest magnitude positive; info float64 [4] = (sweeps run, converged, the largest
+    |g_p . g_q| / (|g_p| |g_q|) met in the last sweep, trace)).  Nothing is read back here: a matrix that did not converge
+    within pca_max_sweeps() sweeps says so in info[1]."""
+    _need_cuda(cov)
+    if cov.dim() != 2 or cov.shape[0] != cov.shape[1]:
+        raise _lib.EvaeError("pca_eigh: a square matrix expected, got %s" % (tuple(cov.shape),))
+    d = cov.shape[0]
+    if not 1 <= d <= pca_max_features():
+        raise _lib.EvaeError("pca_eigh: d=%d outside [1, %d]" % (d, pca_max_features()))
+    _pca_f64("cov", cov, (d, d), "pca_eigh")
+    evals = torch.empty(d, dtype=torch.float64, device=cov.device)
+    evecs = torch.empty((d, d), dtype=torch.float64, device=cov.device)
+    info = torch.empty(4, dtype=torch.float64, device=cov.device)
+    nbytes = _lib.load().evae_pca_eigh_workspace_bytes(d)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=cov.device) if nbytes else None
+    launch.Launcher(cov.device).pca_eigh(cov, d, evals, evecs, info, ws)
+    return evals, evecs, info
+
+
+def pca_project(x, mean, comps, scale=1.0):
+    """out [N x k] float32 = scale (x - mean) comps^T: x [N x d], mean [d] and comps [k x d] float64, 1 <= k <= d; accumulated
+    in fp64, rounded once"""
+    _need_cuda(x, mean, comps)
+    x = _pca_rows(x, "pca_project")
+    N, d = x.shape
+    if comps.dim() != 2 or not 1 <= comps.shape[0] <= d:
+        raise _lib.EvaeError("pca_project: comps must be [k x %d] with 1 <= k <= %d, got %s" % (d, d, tuple(comps.shape)))
+    k = comps.shape[0]
+    _pca_f64("mean", mean, (d,), "pca_project")
+    _pca_f64("comps", comps, (k, d), "pca_project")
+    out = torch.empty((N, k), device=x.device)
+    launch.Launcher(x.device).pca_project(x, N, d, mean, comps, k, scale, out)
+    return out
+
+
+def pca_reconstruct(y, mean, comps):
+    """out [N x d] float32 = mean + y comps: y [N x k], the reverse map of pca_project at scale 1"""
+    _need_cuda(y, mean, comps)
+    y = _pca_rows(y, "pca_reconstruct")
+    N, k = y.shape
+    if comps.dim() != 2 or comps.shape[0] != k or not k <= comps.shape[1] <= pca_max_features():
+        raise _lib.EvaeError("pca_reconstruct: comps must be [%d x d] with %d <= d <= %d, got %s"
+                             % (k, k, pca_max_features(), tuple(comps.shape)))
+    d = comps.shape[1]
+    _pca_f64("mean", mean, (d,), "pca_reconstruct")
+    _pca_f64("comps", comps, (k, d), "pca_reconstruct")
+    out = torch.empty((N, d), device=y.device)
+    launch.Launcher(y.device).pca_reconstruct(y, N, k, mean, comps, d, out)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 # dense layers
 # ------------------------------------------------------------------------------------------------
 # The launches of this section go through evae/launch.py's Launcher (workspace names, entry points, the probe's names), built

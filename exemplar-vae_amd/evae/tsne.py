@@ -6,8 +6,11 @@
 What is computed is method='exact' of scikit-learn -- all N^2 pairs, every iteration, no Barnes-Hut tree -- with its
 gradient-descent rule (gains, momentum 0.5 during the exaggerated phase and 0.8 after it, learning_rate 'auto') plus the
 re-centring of the embedding after every step.  Not carried over: the early exits (`min_grad_norm`,
-`n_iter_without_progress`: all n_iter iterations always run, so n_iter_ == n_iter), init='pca', metrics other than the
-squared Euclidean distance, n_components other than 2, method='barnes_hut'.
+`n_iter_without_progress`: all n_iter iterations always run, so n_iter_ == n_iter), metrics other than the squared Euclidean
+distance, n_components other than 2, method='barnes_hut'.  init='pca' (scikit-learn's default since 1.2; here 'random' stays
+the default) starts from the first two principal components of the input (evae/pca.py, svd_solver 'full' up to rounding, not
+scikit-learn's 'randomized'), rescaled so that the population standard deviation of the first column is 1e-4; no generator is
+touched, so the embedding does not depend on random_state.
 
 The cap on N: a row of distances has to fit one workgroup's LDS during the precision search (64 B + 4 N <= 160 KiB), so
 N <= 32768 (ops.tsne_max_points()).  The dense buffers at the cap: the [N x N] float32 matrix that holds the distances, then
@@ -27,6 +30,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .pca import PCA
 
 EXAGGERATED_ITERS = 250      # scikit-learn's _EXPLORATION_MAX_ITER
 _INIT_STD = 1e-4
@@ -38,8 +42,9 @@ class TSNE:
                  random_state=None, init='random', exaggerated_iters=EXAGGERATED_ITERS, device=None, method='exact'):
         """exaggerated_iters: how many of the n_iter iterations run with early_exaggeration and momentum 0.5 (scikit-learn
         fixes 250; short runs in tests and documents shorten it in proportion).  init: 'random' -- N(0, 1e-4^2) from a
-        torch.Generator on the device seeded with random_state -- or a [N x 2] tensor / array.  device: where a host array
-        given to fit_transform goes (default cuda).  method: 'exact' (dense P, N <= ops.tsne_max_points()) or 'neighbours' (P on
+        torch.Generator on the device seeded with random_state --, 'pca' -- the input's first two principal components with the
+        first column's standard deviation scaled to 1e-4, independent of random_state -- or a [N x 2] tensor / array.  device:
+        where a host array given to fit_transform goes (default cuda).  method: 'exact' (dense P, N <= ops.tsne_max_points()) or 'neighbours' (P on
         the nearest neighbours only, repulsion still exact; N <= ops.tsne_nn_max_points(), perplexity <= 85)."""
         if method not in METHODS:
             raise ValueError("TSNE: method=%r; the choices are 'exact' and 'neighbours' (there is no tree: 'barnes_hut' is not "
@@ -49,8 +54,8 @@ class TSNE:
                              % (perplexity, int(3.0 * float(perplexity) + 1), ops.tsne_nn_max_neighbours()))
         if n_components != 2:
             raise ValueError("TSNE: n_components=%r; the kernels embed in 2 dimensions only" % (n_components,))
-        if not (torch.is_tensor(init) or isinstance(init, np.ndarray) or init == 'random'):
-            raise ValueError("TSNE: init must be 'random' or a [N x 2] tensor (init='pca' is not carried over)")
+        if not (torch.is_tensor(init) or isinstance(init, np.ndarray) or init in ('random', 'pca')):
+            raise ValueError("TSNE: init must be 'random', 'pca' or a [N x 2] tensor")
         if learning_rate != 'auto' and not float(learning_rate) > 0:
             raise ValueError("TSNE: learning_rate must be 'auto' or positive")
         if int(n_iter) < 1 or not 0 <= int(exaggerated_iters):
@@ -60,7 +65,16 @@ class TSNE:
         self.exaggerated_iters, self.device, self.method = int(exaggerated_iters), device, method
         self.embedding_ = self.kl_divergence_ = self.n_iter_ = self.learning_rate_ = None
 
-    def _initial(self, N, device):
+    def _initial(self, N, device, X=None):
+        if isinstance(self.init, str) and self.init == 'pca':
+            if X is None or X.dim() != 2 or X.shape[1] < 2:
+                raise ValueError("TSNE: init='pca' needs an input with at least 2 features")
+            pca = PCA(n_components=2).fit(X)
+            lambda_1 = float(pca._explained_variance_host[0])      # from the one read of fit
+            if not lambda_1 > 0.0:
+                raise ValueError("TSNE: init='pca' on an input without variance (all points equal)")
+            # np.std of the first projected column: the population standard deviation, sqrt(lambda_1 (N - 1) / N)
+            return ops.pca_project(X, pca.mean_, pca.components_, scale=_INIT_STD / np.sqrt(lambda_1 * (N - 1) / N))
         if torch.is_tensor(self.init) or isinstance(self.init, np.ndarray):
             Y = torch.as_tensor(self.init).to(device=device, dtype=torch.float32).clone().contiguous()
             if tuple(Y.shape) != (N, 2):
@@ -80,6 +94,9 @@ class TSNE:
         if len(shape) != 2:
             raise ValueError("TSNE: a [N x zd] input expected, got %s" % (shape,))
         N = shape[0]
+        from_pca = isinstance(self.init, str) and self.init == 'pca'
+        if from_pca and shape[1] < 2:
+            raise ValueError("TSNE: init='pca' needs an input with at least 2 features, got %d" % shape[1])
         if self.perplexity >= N:
             raise ValueError("TSNE: perplexity %g must be less than the number of points %d" % (self.perplexity, N))
         if self.method == 'neighbours' and N > ops.tsne_nn_max_points():
@@ -95,6 +112,8 @@ class TSNE:
             lr = float(self.learning_rate)
         self.learning_rate_ = lr
         with torch.no_grad():
+            # init='pca' can refuse its input (no variance): ahead of the affinity stage, which is the large allocation
+            Y = self._initial(N, X.device, X) if from_pca else None
             if self.method == 'neighbours':
                 csr = ops.tsne_nn_affinities(X, self.perplexity)[:3]
 
@@ -105,7 +124,8 @@ class TSNE:
 
                 def forces(Y, exaggeration, want_kl):
                     return ops.tsne_forces(P, Y, exaggeration, want_kl)
-            Y = self._initial(N, X.device)
+            if Y is None:
+                Y = self._initial(N, X.device)
             velocity = torch.zeros_like(Y)
             gains = torch.ones_like(Y)
             for it in range(self.n_iter):

@@ -1010,6 +1010,41 @@ int evae_nn_rank(const float* z /* [N x zdim] */, int N, int zdim, const int* nb
                  int* rank /* [N x k] */, long long* row_sums /* [N x 2]: penalty, hits */, void* ws, size_t ws_bytes,
                  evae_stream_t stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * PCA of the latent space in fp64 (evae/pca.py; TSNE(init='pca')).  csrc/evae_pca.hip; DESIGN 3.7c.  Inputs are contiguous
+ * fp32 [N x d]; every accumulation is fp64, there are no floating-point atomics and every sum has a fixed order, so equal
+ * inputs give bit-equal outputs.  1 <= d <= evae_pca_max_features() = 256, 2 <= N <= evae_pca_max_points() = 2^20.
+ *
+ * moments: x -> mean [d], cov [d x d] (ddof 1), float64.  Two passes: column sums, then the Gram matrix of the rows centred
+ *   in fp64 (never E[xy] - E[x]E[y]).  A block owns evae_pca_chunk_rows() rows and, in the second pass, a 16 x 16 tile
+ *   (i <= j) of the matrix; partial sums go to ws (evae_pca_workspace_bytes(N, d) bytes), and a finish launch adds the chunks
+ *   in index order, divides by N - 1 and writes cov[i][j] and cov[j][i] from the one value.
+ * eigh: symmetric positive semi-definite cov -> evals [d] descending (ties by original index, clamped at 0), evecs [d x d]
+ *   (row i = component i; in every row the entry of largest magnitude is positive, lowest index on a tie), info [4] =
+ *   { sweeps run, converged (1 / 0), largest |g_p . g_q| / (|g_p| |g_q|) met in the last sweep, trace of cov }.
+ *   ONE workgroup: cyclic one-sided (Hestenes) Jacobi on G = cov, V = I with a round-robin pairing, at most
+ *   evae_pca_max_sweeps() sweeps; a sweep without a pair above 2^-52 |g_p| |g_q| ends the loop (a workgroup-uniform count:
+ *   nothing spins, nothing waits on another workgroup).  A matrix not converged at the bound sets info[1] = 0 and the call
+ *   returns normally.  Eigenvalues are the Rayleigh quotients v^T cov v.  G and V sit in LDS for d <= 96, otherwise in ws
+ *   (evae_pca_eigh_workspace_bytes(d) bytes, 0 for d <= 96: ws may be NULL then).
+ * project: out [N x k] fp32 = scale (x - mean) W^T, W [k x d] float64, 1 <= k <= d; reconstruct: out [N x d] fp32 =
+ *   mean + y W, y [N x k] fp32.  fp64 accumulation, one rounding to fp32.
+ */
+int evae_pca_max_features(void);
+int evae_pca_max_points(void);
+int evae_pca_chunk_rows(void);
+int evae_pca_max_sweeps(void);
+size_t evae_pca_workspace_bytes(int N, int d);
+size_t evae_pca_eigh_workspace_bytes(int d);
+int evae_pca_moments(const float* x /* [N x d] */, int N, int d, double* mean /* [d] */, double* cov /* [d x d] */, void* ws,
+                     size_t ws_bytes, evae_stream_t stream);
+int evae_pca_eigh(const double* cov /* [d x d] */, int d, double* evals /* [d] */, double* evecs /* [d x d] */,
+                  double* info /* [4] */, void* ws, size_t ws_bytes, evae_stream_t stream);
+int evae_pca_project(const float* x /* [N x d] */, int N, int d, const double* mean /* [d] */, const double* W /* [k x d] */,
+                     int k, double scale, float* out /* [N x k] */, evae_stream_t stream);
+int evae_pca_reconstruct(const float* y /* [N x k] */, int N, int k, const double* mean /* [d] */,
+                         const double* W /* [k x d] */, int d, float* out /* [N x d] */, evae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
