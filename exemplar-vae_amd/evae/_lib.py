@@ -273,6 +273,22 @@ SIGNATURES = {
     "evae_pca_eigh": (_i, [_p, _i, _p, _p, _p, _p, _z, _p]),
     "evae_pca_project": (_i, [_p, _i, _i, _p, _p, _i, _d, _p, _p]),
     "evae_pca_reconstruct": (_i, [_p, _i, _i, _p, _p, _i, _p, _p]),
+    "evae_kmeans_max_clusters": (_i, []),
+    "evae_kmeans_max_features": (_i, []),
+    "evae_kmeans_max_points": (_i, []),
+    "evae_kmeans_chunk_rows": (_i, []),
+    "evae_kmeans_centre_tile": (_i, []),
+    "evae_kmeans_workspace_bytes": (_z, [_i, _i, _i]),
+    "evae_kmeans_assign": (_i, [_p, _i, _i, _p, _i, _p, _p, _p]),
+    "evae_kmeans_transform": (_i, [_p, _i, _i, _p, _i, _p, _p]),
+    "evae_kmeans_update": (_i, [_p, _i, _i, _p, _i, _p, _p, _p, _p, _z, _p]),
+    "evae_kmeans_step": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _p, _d, _p, _p, _z, _p]),
+    "evae_kmeans_seed": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _z, _p]),
+    "evae_kmeans_inertia": (_i, [_p, _i, _p, _p, _z, _p]),
+    "evae_cluster_contingency": (_i, [_p, _i, _p, _i, _i, _p, _p]),
+    "evae_cluster_scores": (_i, [_p, _i, _i, _p, _p]),
+    "evae_silhouette_workspace_bytes": (_z, [_i, _i, _i]),
+    "evae_silhouette_samples": (_i, [_p, _i, _i, _p, _p, _i, _p, _p, _z, _i, _p]),
 }
 
 _lib = None

@@ -37,6 +37,7 @@ nothing of a step outlives it.
 """
 import contextlib
 import ctypes as C
+import gc
 import math
 import os
 import time
@@ -511,9 +512,20 @@ class GraphedTrainStep:
                 # keeps those calls from invalidating the capture
                 mode = "thread_local" if shard.is_active() else "global"
                 mode = os.environ.get("EVAE_CAPTURE_MODE", mode)
+                # No cyclic garbage collection while the stream captures: a dead cycle that owns device memory or an older
+                # hipGraph (a finished runner, a traceback) would be destroyed from inside the capture, and what its
+                # destructor calls is not allowed there -- the process aborts.  torch.cuda.graph no longer collects on entry
+                # itself, so such cycles go now, and the collector rests until the capture has ended.
+                gc.collect()
+                gc_was_enabled = gc.isenabled()
+                gc.disable()
                 try:
-                    with torch.cuda.graph(graph, capture_error_mode=mode):
-                        self._body()
+                    try:
+                        with torch.cuda.graph(graph, capture_error_mode=mode):
+                            self._body()
+                    finally:
+                        if gc_was_enabled:
+                            gc.enable()
                     if self.keep_graph:
                         graph.instantiate()      # (a kept graph is not instantiated by the end of its capture)
                     self.opt.finish_capture(self._adam_tables)

@@ -214,6 +214,38 @@ class Launcher:
     def pca_reconstruct(self, y, N, k, mean, W, d, out):
         _lib.check(self.lib.evae_pca_reconstruct(vp(y), N, int(k), vp(mean), vp(W), d, vp(out), self.st), "pca_reconstruct")
 
+    # k-means and clustering scores in fp64 (csrc/evae_kmeans.hip): every buffer and workspace is the caller's
+    def kmeans_assign(self, x, N, d, centres, K, labels, d2):
+        _lib.check(self.lib.evae_kmeans_assign(vp(x), N, d, vp(centres), int(K), vp(labels), vp(d2), self.st), "kmeans_assign")
+
+    def kmeans_transform(self, x, N, d, centres, K, out):
+        _lib.check(self.lib.evae_kmeans_transform(vp(x), N, d, vp(centres), int(K), vp(out), self.st), "kmeans_transform")
+
+    def kmeans_update(self, x, N, d, labels, K, order, start, sums, ws):
+        _lib.check(self.lib.evae_kmeans_update(vp(x), N, d, vp(labels), int(K), vp(order), vp(start), vp(sums), vp(ws), ws.numel(),
+                                               self.st), "kmeans_update")
+
+    def kmeans_step(self, x, N, d, K, centres, labels, d2, order, start, tol_abs, state, ws):
+        _lib.check(self.lib.evae_kmeans_step(vp(x), N, d, int(K), vp(centres), vp(labels), vp(d2), vp(order), vp(start),
+                                             float(tol_abs), vp(state), vp(ws), ws.numel(), self.st), "kmeans_step")
+
+    def kmeans_seed(self, x, N, d, K, u, idx, centres, ws):
+        _lib.check(self.lib.evae_kmeans_seed(vp(x), N, d, int(K), vp(u), vp(idx), vp(centres), vp(ws), ws.numel(), self.st),
+                   "kmeans_seed")
+
+    def kmeans_inertia(self, d2, N, out, ws):
+        _lib.check(self.lib.evae_kmeans_inertia(vp(d2), N, vp(out), vp(ws), ws.numel(), self.st), "kmeans_inertia")
+
+    def cluster_contingency(self, a, Ka, b, Kb, N, table):
+        _lib.check(self.lib.evae_cluster_contingency(vp(a), int(Ka), vp(b), int(Kb), N, vp(table), self.st), "cluster_contingency")
+
+    def cluster_scores(self, table, Ka, Kb, out):
+        _lib.check(self.lib.evae_cluster_scores(vp(table), int(Ka), int(Kb), vp(out), self.st), "cluster_scores")
+
+    def silhouette_samples(self, x, N, d, order, start, K, out, ws, strip_rows):
+        _lib.check(self.lib.evae_silhouette_samples(vp(x), N, d, vp(order), vp(start), int(K), vp(out), vp(ws), ws.numel(),
+                                                    int(strip_rows), self.st), "silhouette_samples")
+
     def bwd_weight_group(self, jobs):
         """ONE launch for up to six thin weight gradients (evae_dense_bwd_weight_group; jobs as wgrad_jobs takes them)"""
         arr, n, _keep = wgrad_jobs(jobs)

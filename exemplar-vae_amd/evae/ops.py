@@ -917,6 +917,217 @@ def pca_reconstruct(y, mean, comps):
 
 
 # ------------------------------------------------------------------------------------------------
+# k-means and clustering scores in fp64 (csrc/evae_kmeans.hip); the driver is evae/cluster.py.  These take what the
+# kernels take and convert nothing: a wrong dtype or a strided tensor is refused, not copied.
+# ------------------------------------------------------------------------------------------------
+KMEANS_STATE = 8     # the record of kmeans_step: iterations, done, labels changed, shift, inertia, relocations, of this step, 0
+
+
+def kmeans_max_clusters():
+    return int(_lib.load().evae_kmeans_max_clusters())
+
+
+def kmeans_max_features():
+    return int(_lib.load().evae_kmeans_max_features())
+
+
+def kmeans_max_points():
+    return int(_lib.load().evae_kmeans_max_points())
+
+
+def kmeans_chunk_rows():
+    """rows of a histogram chunk and positions of a segment of the sorted order"""
+    return int(_lib.load().evae_kmeans_chunk_rows())
+
+
+def kmeans_centre_tile():
+    """centres that pass through LDS together in kmeans_assign"""
+    return int(_lib.load().evae_kmeans_centre_tile())
+
+
+def _km_tensor(name, t, dtype, shape, who):
+    _need_cuda(t)
+    if t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+        raise _lib.EvaeError("%s: %s must be a contiguous %s %s tensor, got %s %s" % (who, name, dtype, list(shape), t.dtype,
+                                                                                     tuple(t.shape)))
+
+
+def _km_rows(x, who, max_points=None):
+    _need_cuda(x)
+    if x.dim() != 2 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise _lib.EvaeError("%s: x must be a contiguous float32 [N x d] tensor, got %s %s" % (who, x.dtype, tuple(x.shape)))
+    N, d = x.shape
+    if not 1 <= d <= kmeans_max_features():
+        raise _lib.EvaeError("%s: %d features outside [1, %d]" % (who, d, kmeans_max_features()))
+    if not 1 <= N <= (max_points or kmeans_max_points()):
+        raise _lib.EvaeError("%s: N=%d outside [1, %d]" % (who, N, max_points or kmeans_max_points()))
+    return N, d
+
+
+def _km_clusters(K, who, N=None):
+    K = int(K)
+    if not 1 <= K <= kmeans_max_clusters() or (N is not None and K > N):
+        raise _lib.EvaeError("%s: K=%d outside [1, min(N, %d)]" % (who, K, kmeans_max_clusters()))
+    return K
+
+
+def kmeans_workspace(N, d, K, device):
+    """the one workspace of the kmeans_* entries for these sizes (a uint8 tensor)"""
+    return torch.empty(_lib.load().evae_kmeans_workspace_bytes(N, d, K), dtype=torch.uint8, device=device)
+
+
+def kmeans_assign(x, centres):
+    """x [N x d] float32, centres [K x d] float64 -> (labels int32 [N], d2 float64 [N]): the nearest centre by
+    sum_k (x_ik - c_jk)^2 in fp64, k ascending, ties to the lowest index; d2 is the winning sum"""
+    N, d = _km_rows(x, "kmeans_assign")
+    _need_cuda(centres)
+    if centres.dim() != 2:
+        raise _lib.EvaeError("kmeans_assign: centres must be [K x %d], got %s" % (d, tuple(centres.shape)))
+    K = _km_clusters(centres.shape[0], "kmeans_assign")
+    _km_tensor("centres", centres, torch.float64, (K, d), "kmeans_assign")
+    labels = torch.empty(N, dtype=torch.int32, device=x.device)
+    d2 = torch.empty(N, dtype=torch.float64, device=x.device)
+    launch.Launcher(x.device).kmeans_assign(x, N, d, centres, K, labels, d2)
+    return labels, d2
+
+
+def kmeans_transform(x, centres):
+    """x [N x d] float32, centres [K x d] float64 -> float32 [N x K]: the distances (not squared) to every centre, the sums of
+    kmeans_assign, one square root and one rounding each"""
+    N, d = _km_rows(x, "kmeans_transform")
+    _need_cuda(centres)
+    if centres.dim() != 2:
+        raise _lib.EvaeError("kmeans_transform: centres must be [K x %d], got %s" % (d, tuple(centres.shape)))
+    K = _km_clusters(centres.shape[0], "kmeans_transform")
+    _km_tensor("centres", centres, torch.float64, (K, d), "kmeans_transform")
+    out = torch.empty((N, K), dtype=torch.float32, device=x.device)
+    launch.Launcher(x.device).kmeans_transform(x, N, d, centres, K, out)
+    return out
+
+
+def kmeans_update(x, labels, K, ws=None):
+    """x [N x d], labels int32 [N] in [0, K) -> (order int32 [N], start int32 [K + 1], sums float64 [K x d]): the stable counting
+    sort of the rows by label (cluster c owns order[start[c] : start[c + 1]], in index order) and the fp64 column sums of every
+    cluster in a fixed order.  A label outside [0, K) is left out of all three (labels are trusted, the kernels only guard)."""
+    N, d = _km_rows(x, "kmeans_update")
+    K = _km_clusters(K, "kmeans_update")
+    _km_tensor("labels", labels, torch.int32, (N,), "kmeans_update")
+    order = torch.empty(N, dtype=torch.int32, device=x.device)
+    start = torch.empty(K + 1, dtype=torch.int32, device=x.device)
+    sums = torch.empty((K, d), dtype=torch.float64, device=x.device)
+    ws = kmeans_workspace(N, d, K, x.device) if ws is None else ws
+    launch.Launcher(x.device).kmeans_update(x, N, d, labels, K, order, start, sums, ws)
+    return order, start, sums
+
+
+def kmeans_state(device):
+    """a zeroed record for kmeans_step"""
+    return torch.zeros(KMEANS_STATE, dtype=torch.float64, device=device)
+
+
+def kmeans_step(x, centres, labels, d2, order, start, tol_abs, state, ws):
+    """One Lloyd iteration in place (assign + update + finish on the current stream): centres [K x d] float64 are replaced by
+    the means of their clusters, labels / d2 / order / start belong to the centres that came in, state (kmeans_state) is advanced.
+    Once state[1] (done) is set, further calls change nothing: a caller may issue several and read the record once."""
+    N, d = _km_rows(x, "kmeans_step")
+    _need_cuda(centres)
+    if centres.dim() != 2:
+        raise _lib.EvaeError("kmeans_step: centres must be [K x %d], got %s" % (d, tuple(centres.shape)))
+    K = _km_clusters(centres.shape[0], "kmeans_step", N)
+    _km_tensor("centres", centres, torch.float64, (K, d), "kmeans_step")
+    _km_tensor("labels", labels, torch.int32, (N,), "kmeans_step")
+    _km_tensor("d2", d2, torch.float64, (N,), "kmeans_step")
+    _km_tensor("order", order, torch.int32, (N,), "kmeans_step")
+    _km_tensor("start", start, torch.int32, (K + 1,), "kmeans_step")
+    _km_tensor("state", state, torch.float64, (KMEANS_STATE,), "kmeans_step")
+    _need_cuda(ws)
+    if not float(tol_abs) >= 0.0:
+        raise _lib.EvaeError("kmeans_step: tol_abs=%r" % (tol_abs,))
+    launch.Launcher(x.device).kmeans_step(x, N, d, K, centres, labels, d2, order, start, tol_abs, state, ws)
+
+
+def kmeans_seed(x, K, u, ws=None):
+    """k-means++ by D^2 sampling from the caller's uniforms: x [N x d], u float64 [K] in [0, 1) -> (idx int32 [K], centres
+    float64 [K x d] = x[idx]).  The first pick is min(floor(u_0 N), N - 1); pick t is the first row whose running sum of
+    min-distances (chunks in order, rows in order) exceeds u_t times their total; when the total is 0 (fewer distinct rows than
+    centres) it is the lowest index not chosen yet.  scikit-learn's greedy local trials are not carried over: one candidate per
+    centre."""
+    N, d = _km_rows(x, "kmeans_seed")
+    K = _km_clusters(K, "kmeans_seed", N)
+    _km_tensor("u", u, torch.float64, (K,), "kmeans_seed")
+    idx = torch.empty(K, dtype=torch.int32, device=x.device)
+    centres = torch.empty((K, d), dtype=torch.float64, device=x.device)
+    ws = kmeans_workspace(N, d, K, x.device) if ws is None else ws
+    launch.Launcher(x.device).kmeans_seed(x, N, d, K, u, idx, centres, ws)
+    return idx, centres
+
+
+def kmeans_inertia(d2):
+    """d2 float64 [N] -> float64 [1]: the sum, chunk sums added in chunk order"""
+    _need_cuda(d2)
+    if d2.dim() != 1 or not 1 <= d2.shape[0] <= kmeans_max_points():
+        raise _lib.EvaeError("kmeans_inertia: d2 must be [N], N in [1, %d], got %s" % (kmeans_max_points(), tuple(d2.shape)))
+    N = d2.shape[0]
+    _km_tensor("d2", d2, torch.float64, (N,), "kmeans_inertia")
+    out = torch.empty(1, dtype=torch.float64, device=d2.device)
+    ws = torch.empty(8 * ((N + kmeans_chunk_rows() - 1) // kmeans_chunk_rows()), dtype=torch.uint8, device=d2.device)
+    launch.Launcher(d2.device).kmeans_inertia(d2, N, out, ws)
+    return out
+
+
+def cluster_contingency(a, Ka, b, Kb):
+    """a, b int32 [N] with values in [0, Ka) and [0, Kb) -> table int64 [Ka x Kb], table[i][j] = #{n : a_n = i, b_n = j}"""
+    _need_cuda(a, b)
+    if a.dim() != 1 or not 1 <= a.shape[0] <= kmeans_max_points():
+        raise _lib.EvaeError("cluster_contingency: a must be [N], N in [1, %d], got %s" % (kmeans_max_points(), tuple(a.shape)))
+    N = a.shape[0]
+    _km_tensor("a", a, torch.int32, (N,), "cluster_contingency")
+    _km_tensor("b", b, torch.int32, (N,), "cluster_contingency")
+    Ka, Kb = _km_clusters(Ka, "cluster_contingency"), _km_clusters(Kb, "cluster_contingency")
+    table = torch.empty((Ka, Kb), dtype=torch.int64, device=a.device)
+    launch.Launcher(a.device).cluster_contingency(a, Ka, b, Kb, N, table)
+    return table
+
+
+CLUSTER_SCORES = ("entropy_a", "entropy_b", "mutual_info", "nmi", "ari", "purity", "n_samples")
+
+
+def cluster_scores(table):
+    """table int64 [Ka x Kb] -> float64 [8] = (H(a), H(b), MI, NMI with the arithmetic mean, ARI, purity = sum_j max_i n_ij / N,
+    N, 0), natural logarithms; one non-empty row and one non-empty column give NMI = ARI = 1"""
+    _need_cuda(table)
+    if table.dim() != 2:
+        raise _lib.EvaeError("cluster_scores: a [Ka x Kb] table expected, got %s" % (tuple(table.shape),))
+    Ka, Kb = _km_clusters(table.shape[0], "cluster_scores"), _km_clusters(table.shape[1], "cluster_scores")
+    _km_tensor("table", table, torch.int64, (Ka, Kb), "cluster_scores")
+    out = torch.empty(8, dtype=torch.float64, device=table.device)
+    launch.Launcher(table.device).cluster_scores(table, Ka, Kb, out)
+    return out
+
+
+def silhouette_samples(x, order, start, strip_rows=0):
+    """x [N x d], (order, start) of kmeans_update -> float64 [N]: s_i = (b_i - a_i) / max(a_i, b_i), a_i the mean distance to the
+    rest of i's cluster, b_i the smallest mean distance to another non-empty cluster; 0 for a singleton and for max(a, b) = 0.
+    Distances are sqrt of pairwise_distance's squared ones, strip by strip (strip_rows query rows, 0: what fits 256 MiB); the
+    result does not depend on strip_rows."""
+    N, d = _km_rows(x, "silhouette_samples", tsne_nn_max_points())
+    if N < 2:
+        raise _lib.EvaeError("silhouette_samples: N=%d, at least 2 rows expected" % N)
+    _need_cuda(start)
+    if start.dim() != 1 or not 2 <= start.shape[0] <= N + 1:
+        raise _lib.EvaeError("silhouette_samples: start must be [K + 1] with 1 <= K <= N=%d, got %s" % (N, tuple(start.shape)))
+    K, strip_rows = start.shape[0] - 1, int(strip_rows)
+    _km_tensor("order", order, torch.int32, (N,), "silhouette_samples")
+    _km_tensor("start", start, torch.int32, (K + 1,), "silhouette_samples")
+    if strip_rows < 0:
+        raise _lib.EvaeError("silhouette_samples: strip_rows=%d (0 = automatic)" % strip_rows)
+    out = torch.zeros(N, dtype=torch.float64, device=x.device)
+    ws = torch.empty(_lib.load().evae_silhouette_workspace_bytes(N, d, strip_rows), dtype=torch.uint8, device=x.device)
+    launch.Launcher(x.device).silhouette_samples(x, N, d, order, start, K, out, ws, strip_rows)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 # dense layers
 # ------------------------------------------------------------------------------------------------
 # The launches of this section go through evae/launch.py's Launcher (workspace names, entry points, the probe's names), built

@@ -1045,6 +1045,66 @@ int evae_pca_project(const float* x /* [N x d] */, int N, int d, const double* m
 int evae_pca_reconstruct(const float* y /* [N x k] */, int N, int k, const double* mean /* [d] */,
                          const double* W /* [k x d] */, int d, float* out /* [N x d] */, evae_stream_t stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * k-means of the latent space and clustering scores in fp64 (evae/cluster.py).  csrc/evae_kmeans.hip; DESIGN 3.7d.  Inputs are
+ * contiguous fp32 [N x d], centres fp64 [K x d]; every accumulation is fp64 in a fixed order, the only atomics are integer ones
+ * (counts), so equal inputs give bit-equal outputs.  1 <= K <= evae_kmeans_max_clusters() = 1024, 1 <= d <=
+ * evae_kmeans_max_features() = 256, 1 <= N <= evae_kmeans_max_points() = 2^20.  One workspace serves every kmeans entry:
+ * evae_kmeans_workspace_bytes(N, d, K) bytes, the caller's.
+ *
+ * assign: labels[i] = argmin_j sum_k (x_ik - c_jk)^2 by direct differences in fp64, k ascending; ties to the lowest j;
+ *   d2[i] = the winning sum.  The centres go through LDS in tiles of evae_kmeans_centre_tile() rows.  No atomics.
+ *   transform: out[i][j] = sqrt of the same sums, rounded once to fp32.
+ * update: a stable counting sort of the rows by label -- order [N] (rows of cluster 0 in index order, then cluster 1, ..) and
+ *   start [K + 1] -- from per-chunk histograms (evae_kmeans_chunk_rows() rows, integer LDS atomics), a scan cluster-major then
+ *   chunk, and each row's count of earlier equal labels in its chunk; then sums [K x d] = the fp64 column sums of every
+ *   cluster: a block owns a segment of chunk_rows positions of the order and adds each run of one cluster in it (partial ->
+ *   slot segment + cluster), a finish adds a cluster's partials in segment order.  A label outside [0, K) is left out.
+ * step: one Lloyd iteration = assign + update + finish on the stream.  state [8] float64 = { iterations done, done (1 / 0),
+ *   labels changed against the previous iteration (N in the first), sum |c_new - c_old|^2, inertia (sum of d2, chunks in order), relocations so
+ *   far, relocations of this iteration, 0 }; the caller zeroes it before the first step.  The finish (one workgroup) gives an
+ *   empty cluster, in ascending index, the point of largest d2 (lowest index on a tie) not taken yet whose cluster keeps a
+ *   member -- subtracted from its donor, labels unchanged --, writes centres = sum / count, and sets done when no label changed
+ *   (never in the first iteration) or the shift is <= tol_abs.  Every kernel of a step returns at its first instruction when
+ *   done is set, so steps may be issued blind; no kernel waits on another.
+ * seed: k-means++ by D^2 sampling from the caller's uniforms u [K] in [0, 1): idx[0] = min(floor(u_0 N), N - 1); then
+ *   d2min = min(d2min, distance to the last pick), running sums chunk by chunk in index order, the pick is the first i whose
+ *   inclusive running sum exceeds u_t total (N - 1 if none does); total == 0 picks the lowest index not chosen yet.
+ *   centres[t] = x[idx[t]].  Two launches per centre.  inertia: out[0] = sum of d2 [N], chunks in order.
+ * contingency: table[a_i][b_i] += 1 (int64 atomics; a label outside its range is left out).  scores: out [8] = { H(a), H(b),
+ *   MI, NMI (arithmetic mean), ARI, purity = sum_j max_i n_ij / N, N, 0 }, one workgroup, natural logarithms, pair counts of
+ *   the ARI exact in int64.  One non-empty row and one non-empty column give NMI = ARI = 1.  Ka, Kb <= 1024.
+ * silhouette: out[i] = (b - a) / max(a, b) from the label-sorted order / start of update: strips of strip_rows rows (0: as
+ *   evae_nn_rank) of evae_pairwise_distance against x[order], one wave per row summing sqrt(d2) over every cluster's segment
+ *   in fp64.  0 for a singleton and for max(a, b) = 0.  2 <= N <= evae_tsne_nn_max_points().
+ */
+int evae_kmeans_max_clusters(void);
+int evae_kmeans_max_features(void);
+int evae_kmeans_max_points(void);
+int evae_kmeans_chunk_rows(void);
+int evae_kmeans_centre_tile(void);
+size_t evae_kmeans_workspace_bytes(int N, int d, int K);
+int evae_kmeans_assign(const float* x /* [N x d] */, int N, int d, const double* centres /* [K x d] */, int K,
+                       int* labels /* [N] */, double* d2 /* [N] */, evae_stream_t stream);
+int evae_kmeans_transform(const float* x /* [N x d] */, int N, int d, const double* centres /* [K x d] */, int K,
+                          float* out /* [N x K] */, evae_stream_t stream);
+int evae_kmeans_update(const float* x /* [N x d] */, int N, int d, const int* labels /* [N] */, int K, int* order /* [N] */,
+                       int* start /* [K + 1] */, double* sums /* [K x d] */, void* ws, size_t ws_bytes, evae_stream_t stream);
+int evae_kmeans_step(const float* x /* [N x d] */, int N, int d, int K, double* centres /* [K x d] */, int* labels /* [N] */,
+                     double* d2 /* [N] */, int* order /* [N] */, int* start /* [K + 1] */, double tol_abs,
+                     double* state /* [8] */, void* ws, size_t ws_bytes, evae_stream_t stream);
+int evae_kmeans_seed(const float* x /* [N x d] */, int N, int d, int K, const double* u /* [K] */, int* idx /* [K] */,
+                     double* centres /* [K x d] */, void* ws, size_t ws_bytes, evae_stream_t stream);
+int evae_kmeans_inertia(const double* d2 /* [N] */, int N, double* out /* [1] */, void* ws, size_t ws_bytes,
+                        evae_stream_t stream);
+int evae_cluster_contingency(const int* a /* [N] */, int Ka, const int* b /* [N] */, int Kb, int N,
+                             long long* table /* [Ka x Kb] */, evae_stream_t stream);
+int evae_cluster_scores(const long long* table /* [Ka x Kb] */, int Ka, int Kb, double* out /* [8] */, evae_stream_t stream);
+size_t evae_silhouette_workspace_bytes(int N, int d, int strip_rows);
+int evae_silhouette_samples(const float* x /* [N x d] */, int N, int d, const int* order /* [N] */,
+                            const int* start /* [K + 1] */, int K, double* out /* [N] */, void* ws, size_t ws_bytes,
+                            int strip_rows, evae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
