@@ -289,6 +289,20 @@ SIGNATURES = {
     "evae_cluster_scores": (_i, [_p, _i, _i, _p, _p]),
     "evae_silhouette_workspace_bytes": (_z, [_i, _i, _i]),
     "evae_silhouette_samples": (_i, [_p, _i, _i, _p, _p, _i, _p, _p, _z, _i, _p]),
+    "evae_gmm_max_components": (_i, []),
+    "evae_gmm_max_features": (_i, [_i]),
+    "evae_gmm_max_points": (_i, []),
+    "evae_gmm_chunk_rows": (_i, []),
+    "evae_gmm_strip_rows": (_i, []),
+    "evae_gmm_max_bytes": (_z, []),
+    "evae_gmm_params_doubles": (_z, [_i, _i, _i]),
+    "evae_gmm_workspace_bytes": (_z, [_i, _i, _i, _i]),
+    "evae_gmm_estep": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _z, _p]),
+    "evae_gmm_mstep": (_i, [_p, _i, _i, _i, _i, _p, _p, _d, _p, _p, _p, _z, _p]),
+    "evae_gmm_step": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _d, _d, _p, _p, _z, _p]),
+    "evae_gmm_prepare": (_i, [_p, _i, _i, _i, _p]),
+    "evae_gmm_argmax": (_i, [_p, _i, _i, _p, _p]),
+    "evae_gmm_sample": (_i, [_p, _i, _i, _i, _p, _p, _i, _p, _p]),
 }
 
 _lib = None

@@ -236,6 +236,28 @@ class Launcher:
     def kmeans_inertia(self, d2, N, out, ws):
         _lib.check(self.lib.evae_kmeans_inertia(vp(d2), N, vp(out), vp(ws), ws.numel(), self.st), "kmeans_inertia")
 
+    # Gaussian mixture in fp64 (csrc/evae_gmm.hip): every buffer and workspace is the caller's
+    def gmm_estep(self, x, N, d, K, ctype, params, log_resp, logp, mean_logp, ws):
+        _lib.check(self.lib.evae_gmm_estep(vp(x), N, d, int(K), int(ctype), vp(params), vp(log_resp), vp(logp), vp(mean_logp),
+                                           vp(ws), ws.numel(), self.st), "gmm_estep")
+
+    def gmm_mstep(self, x, N, d, K, ctype, log_resp, labels, reg_covar, params, state, ws):
+        _lib.check(self.lib.evae_gmm_mstep(vp(x), N, d, int(K), int(ctype), vp(log_resp), vp(labels), float(reg_covar), vp(params),
+                                           vp(state), vp(ws), ws.numel(), self.st), "gmm_mstep")
+
+    def gmm_step(self, x, N, d, K, ctype, params, log_resp, logp, reg_covar, tol, state, ws):
+        _lib.check(self.lib.evae_gmm_step(vp(x), N, d, int(K), int(ctype), vp(params), vp(log_resp), vp(logp), float(reg_covar),
+                                          float(tol), vp(state), vp(ws), ws.numel(), self.st), "gmm_step")
+
+    def gmm_prepare(self, params, d, K, ctype):
+        _lib.check(self.lib.evae_gmm_prepare(vp(params), d, int(K), int(ctype), self.st), "gmm_prepare")
+
+    def gmm_argmax(self, log_resp, N, K, labels):
+        _lib.check(self.lib.evae_gmm_argmax(vp(log_resp), N, int(K), vp(labels), self.st), "gmm_argmax")
+
+    def gmm_sample(self, params, d, K, ctype, comp, eps, n, z):
+        _lib.check(self.lib.evae_gmm_sample(vp(params), d, int(K), int(ctype), vp(comp), vp(eps), n, vp(z), self.st), "gmm_sample")
+
     def cluster_contingency(self, a, Ka, b, Kb, N, table):
         _lib.check(self.lib.evae_cluster_contingency(vp(a), int(Ka), vp(b), int(Kb), N, vp(table), self.st), "cluster_contingency")
 

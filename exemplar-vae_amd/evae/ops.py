@@ -1128,6 +1128,190 @@ def silhouette_samples(x, order, start, strip_rows=0):
 
 
 # ------------------------------------------------------------------------------------------------
+# Gaussian mixture in fp64 (csrc/evae_gmm.hip); the driver is evae/mixture.py.  Like the kmeans_* entries these
+# take what the kernels take and convert nothing.  The parameters of a mixture live in ONE float64 buffer (gmm_params) that
+# gmm_views slices without copying.
+# ------------------------------------------------------------------------------------------------
+GMM_STATE = 8        # the record of gmm_step: iterations, done, converged, lower bound, previous lower bound, failed component, 0, 0
+GMM_TYPES = {'full': 0, 'diag': 1, 'spherical': 2}
+
+
+def gmm_max_components():
+    return int(_lib.load().evae_gmm_max_components())
+
+
+def gmm_max_features(covariance_type='full'):
+    """96 for 'full' (the factor of a component lives in LDS), 256 for 'diag' and 'spherical'"""
+    return int(_lib.load().evae_gmm_max_features(GMM_TYPES[covariance_type]))
+
+
+def gmm_max_points():
+    return int(_lib.load().evae_gmm_max_points())
+
+
+def gmm_chunk_rows():
+    """rows whose weighted sums are formed together in the M-step"""
+    return int(_lib.load().evae_gmm_chunk_rows())
+
+
+def gmm_strip_rows():
+    """rows a block of the E-step owns"""
+    return int(_lib.load().evae_gmm_strip_rows())
+
+
+def gmm_max_bytes():
+    """log_resp plus workspace may not exceed this"""
+    return int(_lib.load().evae_gmm_max_bytes())
+
+
+def gmm_workspace_bytes(N, d, K, covariance_type):
+    return int(_lib.load().evae_gmm_workspace_bytes(int(N), int(d), int(K), GMM_TYPES[covariance_type]))
+
+
+def gmm_check_sizes(N, d, K, covariance_type, who):
+    """what the kernels refuse, from the sizes alone: before any allocation or launch"""
+    if covariance_type not in GMM_TYPES:
+        raise _lib.EvaeError("%s: covariance_type=%r; one of %s expected" % (who, covariance_type, sorted(GMM_TYPES)))
+    if not 1 <= K <= gmm_max_components():
+        raise _lib.EvaeError("%s: K=%d outside [1, %d]" % (who, K, gmm_max_components()))
+    if not 1 <= d <= gmm_max_features(covariance_type):
+        raise _lib.EvaeError("%s: %d features outside [1, %d] for covariance_type=%r" % (who, d, gmm_max_features(covariance_type),
+                                                                                        covariance_type))
+    if N is None:
+        return
+    if not 1 <= N <= gmm_max_points():
+        raise _lib.EvaeError("%s: N=%d outside [1, %d]" % (who, N, gmm_max_points()))
+    resp, ws = 8 * N * K, gmm_workspace_bytes(N, d, K, covariance_type)
+    if resp + ws > gmm_max_bytes():
+        raise _lib.EvaeError("%s: log_resp of %d bytes plus a workspace of %d bytes for N=%d, d=%d, K=%d exceed %d bytes"
+                             % (who, resp, ws, N, d, K, gmm_max_bytes()))
+
+
+def _gmm_rows(x, who):
+    _need_cuda(x)
+    if x.dim() != 2 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise _lib.EvaeError("%s: x must be a contiguous float32 [N x d] tensor, got %s %s" % (who, x.dtype, tuple(x.shape)))
+    return x.shape
+
+
+def gmm_params(d, K, covariance_type, device):
+    """an uninitialised parameter buffer (float64) for these sizes"""
+    gmm_check_sizes(None, d, K, covariance_type, "gmm_params")
+    n = _lib.load().evae_gmm_params_doubles(int(d), int(K), GMM_TYPES[covariance_type])
+    return torch.empty(n, dtype=torch.float64, device=device)
+
+
+def gmm_views(params, d, K, covariance_type):
+    """-> dict of views into a parameter buffer: weights [K], nk [K], log_det [K], means [K x d], b [K x d], covariances and
+    precisions_cholesky ([K x d x d], [K x d] or [K])"""
+    cs = {'full': d * d, 'diag': d, 'spherical': 1}[covariance_type]
+    shape = {'full': (K, d, d), 'diag': (K, d), 'spherical': (K,)}[covariance_type]
+    o = 3 * K
+    return dict(weights=params[0:K], nk=params[K:2 * K], log_det=params[2 * K:3 * K], means=params[o:o + K * d].view(K, d),
+                b=params[o + K * d:o + 2 * K * d].view(K, d), covariances=params[o + 2 * K * d:o + 2 * K * d + K * cs].view(shape),
+                precisions_cholesky=params[o + 2 * K * d + K * cs:o + 2 * K * d + 2 * K * cs].view(shape))
+
+
+def _gmm_args(x, params, K, covariance_type, who):
+    N, d = _gmm_rows(x, who)
+    gmm_check_sizes(N, d, int(K), covariance_type, who)
+    n = _lib.load().evae_gmm_params_doubles(d, int(K), GMM_TYPES[covariance_type])
+    _km_tensor("params", params, torch.float64, (n,), who)
+    return N, d, int(K), GMM_TYPES[covariance_type]
+
+
+def gmm_workspace(N, d, K, covariance_type, device):
+    """the one workspace of the gmm_* entries for these sizes (a uint8 tensor)"""
+    return torch.empty(gmm_workspace_bytes(N, d, K, covariance_type), dtype=torch.uint8, device=device)
+
+
+def gmm_state(device):
+    """a zeroed record for gmm_step / gmm_mstep"""
+    return torch.zeros(GMM_STATE, dtype=torch.float64, device=device)
+
+
+def gmm_estep(x, params, K, covariance_type, ws=None, log_resp=None, logp=None):
+    """x [N x d] float32 -> (log_resp float64 [N x K], logp float64 [N] = log p(x_i), mean_logp float64 [1])"""
+    N, d, K, t = _gmm_args(x, params, K, covariance_type, "gmm_estep")
+    log_resp = torch.empty((N, K), dtype=torch.float64, device=x.device) if log_resp is None else log_resp
+    logp = torch.empty(N, dtype=torch.float64, device=x.device) if logp is None else logp
+    _km_tensor("log_resp", log_resp, torch.float64, (N, K), "gmm_estep")
+    _km_tensor("logp", logp, torch.float64, (N,), "gmm_estep")
+    mean = torch.empty(1, dtype=torch.float64, device=x.device)
+    ws = gmm_workspace(N, d, K, covariance_type, x.device) if ws is None else ws
+    _need_cuda(ws)
+    launch.Launcher(x.device).gmm_estep(x, N, d, K, t, params, log_resp, logp, mean, ws)
+    return log_resp, logp, mean
+
+
+def gmm_mstep(x, params, K, covariance_type, reg_covar, state, log_resp=None, labels=None, ws=None):
+    """The parameters in `params` from responsibilities: log_resp float64 [N x K] (r = exp) or labels int32 [N] (one-hot),
+    exactly one of them.  state[5] names the lowest component whose covariance is not positive definite (-1: none)."""
+    N, d, K, t = _gmm_args(x, params, K, covariance_type, "gmm_mstep")
+    if (log_resp is None) == (labels is None):
+        raise _lib.EvaeError("gmm_mstep: exactly one of log_resp and labels expected")
+    if log_resp is not None:
+        _km_tensor("log_resp", log_resp, torch.float64, (N, K), "gmm_mstep")
+    else:
+        _km_tensor("labels", labels, torch.int32, (N,), "gmm_mstep")
+    _km_tensor("state", state, torch.float64, (GMM_STATE,), "gmm_mstep")
+    if not float(reg_covar) >= 0.0:
+        raise _lib.EvaeError("gmm_mstep: reg_covar=%r" % (reg_covar,))
+    ws = gmm_workspace(N, d, K, covariance_type, x.device) if ws is None else ws
+    _need_cuda(ws)
+    launch.Launcher(x.device).gmm_mstep(x, N, d, K, t, log_resp, labels, reg_covar, params, state, ws)
+
+
+def gmm_step(x, params, K, covariance_type, log_resp, logp, reg_covar, tol, state, ws):
+    """One EM iteration in place (E-step, M-step, record: six launches on the current stream).  Once state[1] (done) is set,
+    further calls change nothing: a caller may issue several and read the record once."""
+    N, d, K, t = _gmm_args(x, params, K, covariance_type, "gmm_step")
+    _km_tensor("log_resp", log_resp, torch.float64, (N, K), "gmm_step")
+    _km_tensor("logp", logp, torch.float64, (N,), "gmm_step")
+    _km_tensor("state", state, torch.float64, (GMM_STATE,), "gmm_step")
+    _need_cuda(ws)
+    if not float(reg_covar) >= 0.0 or not float(tol) >= 0.0:
+        raise _lib.EvaeError("gmm_step: reg_covar=%r, tol=%r" % (reg_covar, tol))
+    launch.Launcher(x.device).gmm_step(x, N, d, K, t, params, log_resp, logp, reg_covar, tol, state, ws)
+
+
+def gmm_prepare(params, d, K, covariance_type):
+    """b = mu P and log_det = sum log diag P from the means and factors already in params"""
+    gmm_check_sizes(None, d, int(K), covariance_type, "gmm_prepare")
+    n = _lib.load().evae_gmm_params_doubles(int(d), int(K), GMM_TYPES[covariance_type])
+    _km_tensor("params", params, torch.float64, (n,), "gmm_prepare")
+    launch.Launcher(params.device).gmm_prepare(params, int(d), int(K), GMM_TYPES[covariance_type])
+
+
+def gmm_argmax(log_resp):
+    """float64 [N x K] -> int32 [N]: the first of the largest entries of every row"""
+    _need_cuda(log_resp)
+    if log_resp.dim() != 2 or not 1 <= log_resp.shape[0] <= gmm_max_points() or not 1 <= log_resp.shape[1] <= gmm_max_components():
+        raise _lib.EvaeError("gmm_argmax: log_resp must be [N x K] within the caps, got %s" % (tuple(log_resp.shape),))
+    N, K = log_resp.shape
+    _km_tensor("log_resp", log_resp, torch.float64, (N, K), "gmm_argmax")
+    labels = torch.empty(N, dtype=torch.int32, device=log_resp.device)
+    launch.Launcher(log_resp.device).gmm_argmax(log_resp, N, K, labels)
+    return labels
+
+
+def gmm_sample(params, d, K, covariance_type, comp, eps):
+    """comp int32 [n] in [0, K), eps float64 [n x d] standard normals -> float32 [n x d]: mu_c + (P_c^T)^-1 eps"""
+    gmm_check_sizes(None, d, int(K), covariance_type, "gmm_sample")
+    n_par = _lib.load().evae_gmm_params_doubles(int(d), int(K), GMM_TYPES[covariance_type])
+    _km_tensor("params", params, torch.float64, (n_par,), "gmm_sample")
+    _need_cuda(comp, eps)
+    if comp.dim() != 1 or not 1 <= comp.shape[0] <= gmm_max_points():
+        raise _lib.EvaeError("gmm_sample: comp must be [n], n in [1, %d], got %s" % (gmm_max_points(), tuple(comp.shape)))
+    n = comp.shape[0]
+    _km_tensor("comp", comp, torch.int32, (n,), "gmm_sample")
+    _km_tensor("eps", eps, torch.float64, (n, d), "gmm_sample")
+    z = torch.empty((n, d), dtype=torch.float32, device=params.device)
+    launch.Launcher(params.device).gmm_sample(params, int(d), int(K), GMM_TYPES[covariance_type], comp, eps, n, z)
+    return z
+
+
+# ------------------------------------------------------------------------------------------------
 # dense layers
 # ------------------------------------------------------------------------------------------------
 # The launches of this section go through evae/launch.py's Launcher (workspace names, entry points, the probe's names), built

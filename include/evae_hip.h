@@ -1105,6 +1105,52 @@ int evae_silhouette_samples(const float* x /* [N x d] */, int N, int d, const in
                             const int* start /* [K + 1] */, int K, double* out /* [N] */, void* ws, size_t ws_bytes,
                             int strip_rows, evae_stream_t stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Gaussian mixture of the latent space in fp64: EM, densities, sampling (evae/mixture.py).  csrc/evae_gmm.hip; DESIGN 3.7e.
+ * Inputs are contiguous fp32 [N x d]; every accumulation is fp64 in a fixed order, the only atomic is an integer minimum, so
+ * equal inputs give bit-equal outputs.  type: 0 'full', 1 'diag', 2 'spherical'.  1 <= K <= evae_gmm_max_components() = 256,
+ * 1 <= N <= evae_gmm_max_points() = 2^20, 1 <= d <= evae_gmm_max_features(type) = 96 ('full': the factor lives in LDS) or 256;
+ * a shape whose log_resp [N x K] plus workspace exceed evae_gmm_max_bytes() = 2^30 is refused.  Every buffer is the caller's.
+ *
+ * params: one fp64 buffer of evae_gmm_params_doubles(d, K, type): weights [K] | n_k [K] | log_det [K] | means [K x d] |
+ *   b [K x d] | cov [K x cs] | prec [K x cs], cs = d*d, d or 1.  prec is P_k, upper triangular, P_k P_k^T = Sigma_k^-1
+ *   (a vector 1 / sqrt(var) for 'diag', a scalar for 'spherical'); b_k = mu_k P_k; log_det_k = sum_j log P_k[j,j].
+ * estep: log_resp[i][k] = log pi_k + log N(x_i | k) - log p(x_i), logp[i] = log p(x_i), mean_logp[0] = their mean (strips of
+ *   evae_gmm_strip_rows() rows in row order, then the strips in order).  log N = -(d log 2 pi + sum_j y_j^2) / 2 + log_det_k,
+ *   y = x P_k - b_k, every sum in ascending index; the log-sum-exp subtracts the row maximum, k ascending.
+ * mstep: from log_resp (r = exp) or from int32 labels (one-hot), exactly one of them: n_k = sum r + 10 eps, means, covariances
+ *   about the new means (chunks of evae_gmm_chunk_rows() rows in index order) + reg_covar, the factors, b, log_det, weights
+ *   = n_k / sum n.  state[5] = the lowest component whose covariance is not positive definite (-1: none; then state[1] = 1
+ *   and that component's prec, b and log_det are left as they were).
+ * step: one EM iteration as scikit-learn's loop has it: estep, mstep, then |bound - previous| < tol.  state [8]: iterations,
+ *   done, converged, lower bound (of this estep: the parameters before this mstep), previous lower bound, failed component,
+ *   0, 0.  Zero it before the first step.  Once done is set further steps change nothing.  Six launches.
+ * prepare: b and log_det from the means and prec already in params (an initialisation that brings its own).
+ * argmax: labels[i] = the first k of the largest log_resp[i][k].
+ * sample: z[i] = mu_c + (P_c^T)^-1 eps[i] with c = comp[i], by forward substitution in fp64, rounded once to fp32.
+ */
+int evae_gmm_max_components(void);
+int evae_gmm_max_features(int type);
+int evae_gmm_max_points(void);
+int evae_gmm_chunk_rows(void);
+int evae_gmm_strip_rows(void);
+size_t evae_gmm_max_bytes(void);
+size_t evae_gmm_params_doubles(int d, int K, int type);
+size_t evae_gmm_workspace_bytes(int N, int d, int K, int type);
+int evae_gmm_estep(const float* x /* [N x d] */, int N, int d, int K, int type, const double* params,
+                   double* log_resp /* [N x K] */, double* logp /* [N] */, double* mean_logp /* [1] */, void* ws,
+                   size_t ws_bytes, evae_stream_t stream);
+int evae_gmm_mstep(const float* x /* [N x d] */, int N, int d, int K, int type, const double* log_resp /* [N x K] or NULL */,
+                   const int* labels /* [N] or NULL */, double reg_covar, double* params, double* state /* [8] */, void* ws,
+                   size_t ws_bytes, evae_stream_t stream);
+int evae_gmm_step(const float* x /* [N x d] */, int N, int d, int K, int type, double* params, double* log_resp /* [N x K] */,
+                  double* logp /* [N] */, double reg_covar, double tol, double* state /* [8] */, void* ws, size_t ws_bytes,
+                  evae_stream_t stream);
+int evae_gmm_prepare(double* params, int d, int K, int type, evae_stream_t stream);
+int evae_gmm_argmax(const double* log_resp /* [N x K] */, int N, int K, int* labels /* [N] */, evae_stream_t stream);
+int evae_gmm_sample(const double* params, int d, int K, int type, const int* comp /* [n] */, const double* eps /* [n x d] */,
+                    int n, float* z /* [n x d] */, evae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
