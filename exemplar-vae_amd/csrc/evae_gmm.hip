@@ -27,7 +27,7 @@
 //   EARLIER launch of the stream: nothing polls, nothing waits on another workgroup.  A step is six launches.
 #include <float.h>
 
-#include "evae_common.h"
+#include "evae_latent.h"
 
 namespace evae {
 
@@ -43,7 +43,6 @@ constexpr int kGmSub = 64;                                   // centred rows of 
 constexpr int kGmMaxTri = kGmMaxDFull * (kGmMaxDFull + 1) / 2;
 constexpr int kGmPerThread = (kGmMaxTri + kGmThreads - 1) / kGmThreads;   // 19
 constexpr int kGmOneThreads = 1024;
-constexpr int kGmNone = 0x7fffffff;
 constexpr size_t kGmMaxBytes = (size_t)1 << 30;
 constexpr int kGmLdsBudget = 150 * 1024;
 constexpr double kGmLog2Pi = 1.8378770664093454835606594728112;
@@ -71,8 +70,6 @@ __host__ __device__ inline GmParams gm_params(double* p, int d, int K, int type)
   return q;
 }
 
-__device__ __forceinline__ bool gm_done(const double* state) { return state != nullptr && state[1] != 0.0; }
-
 // ---------------------------------------------------------------- E-step
 static int gm_factor_doubles(int d, int type) { return type == kGmFull ? d * (d + 1) / 2 : (type == kGmDiag ? d : 1); }
 static size_t gm_estep_rows_bytes(int d) { return (size_t)kGmStrip * (d | 1) * sizeof(float) + kGmStrip * sizeof(double); }
@@ -89,7 +86,7 @@ template <int TYPE>
 __global__ __launch_bounds__(kGmThreads) void gmm_estep_kernel(const float* __restrict__ x, int N, int d, int K, double* params,
                                                                int T, double* log_resp, double* __restrict__ logp,
                                                                double* __restrict__ strip_sum, const double* state) {
-  if (gm_done(state)) return;
+  if (step_done(state)) return;
   extern __shared__ __attribute__((aligned(16))) double gm_smem[];
   const GmParams q = gm_params(params, d, K, TYPE);
   const int ps = TYPE == kGmFull ? d * (d + 1) / 2 : (TYPE == kGmDiag ? d : 1);
@@ -170,12 +167,12 @@ __global__ __launch_bounds__(kGmThreads) void gmm_wsum_kernel(const float* __res
                                                               const double* __restrict__ log_resp, const int* __restrict__ labels,
                                                               const double* __restrict__ mu, double* __restrict__ partial,
                                                               int* fail, const double* state) {
-  if (gm_done(state)) return;
+  if (step_done(state)) return;
   __shared__ double rr[kGmChunk];
   __shared__ double part[kGmThreads];
   const int tid = threadIdx.x, k = blockIdx.y, c0 = blockIdx.x * kGmChunk, n = min(kGmChunk, N - c0);
   const int cols = MODE == 0 ? d + 1 : d;
-  if (MODE == 0 && fail && tid == 0 && blockIdx.x == 0 && k == 0) *fail = kGmNone;   // read by the finish of this same pass
+  if (MODE == 0 && fail && tid == 0 && blockIdx.x == 0 && k == 0) *fail = kNoIndex;   // read by the finish of this same pass
   for (int e = tid; e < kGmChunk; e += kGmThreads) {
     double v = 0.0;
     if (e < n) v = log_resp ? exp(log_resp[(size_t)(c0 + e) * K + k]) : (labels[c0 + e] == k ? 1.0 : 0.0);
@@ -214,7 +211,7 @@ __global__ __launch_bounds__(kGmThreads) void gmm_wsum_kernel(const float* __res
 
 __global__ __launch_bounds__(kGmThreads) void gmm_means_kernel(const double* __restrict__ partial, int chunks, int d, int K,
                                                                double* params, int type, const double* state) {
-  if (gm_done(state)) return;
+  if (step_done(state)) return;
   const int idx = blockIdx.x * kGmThreads + threadIdx.x, cols = d + 1;
   if (idx >= K * cols) return;
   const int k = idx / cols, c = idx - k * cols;
@@ -247,7 +244,7 @@ __global__ __launch_bounds__(kGmThreads) void gmm_scatter_kernel(const float* __
                                                                  const double* __restrict__ log_resp,
                                                                  const int* __restrict__ labels, const double* __restrict__ mu,
                                                                  double* __restrict__ partial, const double* state) {
-  if (gm_done(state)) return;
+  if (step_done(state)) return;
   extern __shared__ __attribute__((aligned(16))) double gm_smem[];
   const int ldc = d | 1, E = d * (d + 1) / 2;
   double* xc = gm_smem;                                            // [kGmSub x ldc]
@@ -303,7 +300,7 @@ static size_t gm_finish_lds(int d, int type) {
 template <int TYPE>
 __global__ __launch_bounds__(kGmThreads) void gmm_finish_kernel(const double* __restrict__ partial, int chunks, int d, int K,
                                                                 double reg, double* params, int* fail, const double* state) {
-  if (gm_done(state)) return;
+  if (step_done(state)) return;
   extern __shared__ __attribute__((aligned(16))) double gm_smem[];
   const int tid = threadIdx.x, k = blockIdx.x;
   const GmParams q = gm_params(params, d, K, TYPE);
@@ -449,6 +446,7 @@ __global__ __launch_bounds__(kGmThreads) void gmm_prepare_kernel(int d, int K, i
 }
 
 // ---------------------------------------------------------------- record
+// Not ordered_total: contiguous slices per thread, then the 1024 partial sums in thread order -- another association, other bits.
 __device__ __forceinline__ double gm_strip_total(const double* __restrict__ strip_sum, int strips, double* buf) {
   const int tid = threadIdx.x, S = (strips + kGmOneThreads - 1) / kGmOneThreads;
   double s = 0.0;
@@ -484,12 +482,12 @@ __device__ __forceinline__ void gm_weights(const GmParams& q, int K, double* buf
 __global__ __launch_bounds__(kGmOneThreads) void gmm_record_kernel(double* params, int d, int K, int type,
                                                                    const double* __restrict__ strip_sum, int strips, int N,
                                                                    double tol, const int* fail, int advance, double* state) {
-  if (advance && gm_done(state)) return;
+  if (advance && step_done(state)) return;
   __shared__ double buf[kGmOneThreads];
   const GmParams q = gm_params(params, d, K, type);
   gm_weights(q, K, buf);
   const int f = *fail;
-  const double failed = f == kGmNone ? -1.0 : (double)f;
+  const double failed = f == kNoIndex ? -1.0 : (double)f;
   if (!advance) {
     if (threadIdx.x == 0) {
       state[5] = failed;
@@ -585,55 +583,32 @@ static int gm_entries(int d, int type) { return type == kGmFull ? d * (d + 1) / 
 
 static GmLayout gm_layout(int N, int d, int K, int type) {
   GmLayout w;
-  size_t o = 0;
-  auto take = [&o](size_t bytes) {
-    const size_t at = o;
-    o += align_up(bytes, 256);
-    return at;
-  };
+  WsCursor ws;
   const size_t chunks = (size_t)gm_chunks(N);
-  w.part1 = take(chunks * K * (d + 1) * sizeof(double));
-  w.part2 = take(chunks * K * gm_entries(d, type) * sizeof(double));
-  w.strip = take((size_t)gm_strips(N) * sizeof(double));
-  w.fail = take(sizeof(int));
-  w.bytes = o;
+  w.part1 = ws.take(chunks * K * (d + 1) * sizeof(double));
+  w.part2 = ws.take(chunks * K * gm_entries(d, type) * sizeof(double));
+  w.strip = ws.take((size_t)gm_strips(N) * sizeof(double));
+  w.fail = ws.take(sizeof(int));
+  w.bytes = ws.o;
   return w;
 }
 
+// Only a wide input needs more LDS than a launch gets unasked; then the most a workgroup may have, less what is static.
 static int gm_lds_attr(const void* fn, size_t bytes, const char* what) {
-  // Only a wide input needs more LDS than a launch gets unasked.  Where it is needed, at every call, not once per process:
-  // the attribute belongs to the function on the CURRENT device.
-  if (bytes <= 32 * 1024) return EVAE_OK;
-  const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048);
-  if (e != hipSuccess) {
-    set_error("%s: %zu bytes of LDS refused: %s", what, bytes, hipGetErrorString(e));
-    return EVAE_ELAUNCH;
-  }
-  return EVAE_OK;
+  return bytes <= 32 * 1024 ? EVAE_OK : set_max_lds(fn, 160 * 1024 - 2048, what);
 }
-
-static bool gm_aligned8(const void* p) { return ((uintptr_t)p & 7) == 0; }
 
 static int gm_estep_launch(const float* x, int N, int d, int K, int type, double* params, double* log_resp, double* logp,
                            char* ws, const GmLayout& w, const double* state, hipStream_t stream) {
   const int T = gm_estep_tile(d, type);
   const size_t lds = gm_estep_lds(d, type);
   double* strip = reinterpret_cast<double*>(ws + w.strip);
-  const void* fn = type == kGmFull ? (const void*)gmm_estep_kernel<kGmFull>
-                                   : (type == kGmDiag ? (const void*)gmm_estep_kernel<kGmDiag> : (const void*)gmm_estep_kernel<kGmSph>);
-  int rc = gm_lds_attr(fn, lds, "gmm_estep");
+  const auto estep = type == kGmFull ? gmm_estep_kernel<kGmFull>
+                                     : (type == kGmDiag ? gmm_estep_kernel<kGmDiag> : gmm_estep_kernel<kGmSph>);
+  int rc = gm_lds_attr((const void*)estep, lds, "gmm_estep");
   if (rc) return rc;
-  const int blocks = gm_strips(N);
-  if (type == kGmFull) gmm_estep_kernel<kGmFull><<<blocks, kGmThreads, lds, stream>>>(x, N, d, K, params, T, log_resp, logp, strip, state);
-  else if (type == kGmDiag) gmm_estep_kernel<kGmDiag><<<blocks, kGmThreads, lds, stream>>>(x, N, d, K, params, T, log_resp, logp, strip, state);
-  else gmm_estep_kernel<kGmSph><<<blocks, kGmThreads, lds, stream>>>(x, N, d, K, params, T, log_resp, logp, strip, state);
+  estep<<<gm_strips(N), kGmThreads, lds, stream>>>(x, N, d, K, params, T, log_resp, logp, strip, state);
   return check_launch("gmm_estep_kernel");
-}
-
-static int gm_pow2_width(int cols) {
-  int W = 1;
-  while (W < cols && W < kGmThreads) W <<= 1;
-  return W;
 }
 
 // pass 1, means, pass 2, finish: everything of the M-step but the weights
@@ -645,7 +620,10 @@ static int gm_mstep_launch(const float* x, int N, int d, int K, int type, const 
   double* part2 = reinterpret_cast<double*>(ws + w.part2);
   int* fail = reinterpret_cast<int*>(ws + w.fail);
   const dim3 grid(chunks, K);
-  gmm_wsum_kernel<0><<<grid, kGmThreads, 0, stream>>>(x, N, d, K, gm_pow2_width(d + 1), log_resp, labels, nullptr, part1, fail, state);
+  const auto finish = type == kGmFull ? gmm_finish_kernel<kGmFull>
+                                      : (type == kGmDiag ? gmm_finish_kernel<kGmDiag> : gmm_finish_kernel<kGmSph>);
+  gmm_wsum_kernel<0><<<grid, kGmThreads, 0, stream>>>(x, N, d, K, pow2_width(d + 1, kGmThreads), log_resp, labels, nullptr, part1, fail,
+                                                      state);
   int rc = check_launch("gmm_wsum_kernel<0>");
   if (rc) return rc;
   gmm_means_kernel<<<(K * (d + 1) + kGmThreads - 1) / kGmThreads, kGmThreads, 0, stream>>>(part1, chunks, d, K, params, type, state);
@@ -654,14 +632,14 @@ static int gm_mstep_launch(const float* x, int N, int d, int K, int type, const 
     if ((rc = gm_lds_attr((const void*)gmm_scatter_kernel, gm_scatter_lds(d), "gmm_scatter"))) return rc;
     gmm_scatter_kernel<<<grid, kGmThreads, gm_scatter_lds(d), stream>>>(x, N, d, K, log_resp, labels, q.mu, part2, state);
     if ((rc = check_launch("gmm_scatter_kernel"))) return rc;
-    if ((rc = gm_lds_attr((const void*)gmm_finish_kernel<kGmFull>, gm_finish_lds(d, type), "gmm_finish"))) return rc;
-    gmm_finish_kernel<kGmFull><<<K, kGmThreads, gm_finish_lds(d, type), stream>>>(part2, chunks, d, K, reg, params, fail, state);
   } else {
-    gmm_wsum_kernel<1><<<grid, kGmThreads, 0, stream>>>(x, N, d, K, gm_pow2_width(d), log_resp, labels, q.mu, part2, nullptr, state);
+    gmm_wsum_kernel<1><<<grid, kGmThreads, 0, stream>>>(x, N, d, K, pow2_width(d, kGmThreads), log_resp, labels, q.mu, part2, nullptr,
+                                                        state);
     if ((rc = check_launch("gmm_wsum_kernel<1>"))) return rc;
-    if (type == kGmDiag) gmm_finish_kernel<kGmDiag><<<K, kGmThreads, gm_finish_lds(d, type), stream>>>(part2, chunks, d, K, reg, params, fail, state);
-    else gmm_finish_kernel<kGmSph><<<K, kGmThreads, gm_finish_lds(d, type), stream>>>(part2, chunks, d, K, reg, params, fail, state);
   }
+  // (only 'full' can be wide enough to ask for more LDS here: the others hold d + 2 doubles)
+  if ((rc = gm_lds_attr((const void*)finish, gm_finish_lds(d, type), "gmm_finish"))) return rc;
+  finish<<<K, kGmThreads, gm_finish_lds(d, type), stream>>>(part2, chunks, d, K, reg, params, fail, state);
   return check_launch("gmm_finish_kernel");
 }
 
@@ -707,7 +685,7 @@ extern "C" int evae_gmm_estep(const float* x, int N, int d, int K, int type, con
   hipStream_t stream = (hipStream_t)stream_;
   GM_SIZES("gmm_estep");
   EVAE_REQUIRE(x && params && log_resp && logp && mean_logp, "gmm_estep: null pointer");
-  EVAE_REQUIRE(gm_aligned8(params) && gm_aligned8(log_resp) && gm_aligned8(logp) && gm_aligned8(mean_logp),
+  EVAE_REQUIRE(aligned8(params) && aligned8(log_resp) && aligned8(logp) && aligned8(mean_logp),
                "gmm_estep: misaligned pointer");
   const GmLayout w = gm_layout(N, d, K, type);
   char* base = static_cast<char*>(ws);
@@ -723,7 +701,7 @@ extern "C" int evae_gmm_mstep(const float* x, int N, int d, int K, int type, con
   GM_SIZES("gmm_mstep");
   EVAE_REQUIRE(x && params && state, "gmm_mstep: null pointer");
   EVAE_REQUIRE((log_resp != nullptr) != (labels != nullptr), "gmm_mstep: exactly one of log_resp and labels expected");
-  EVAE_REQUIRE(gm_aligned8(params) && gm_aligned8(log_resp) && gm_aligned8(state), "gmm_mstep: misaligned pointer");
+  EVAE_REQUIRE(aligned8(params) && aligned8(log_resp) && aligned8(state), "gmm_mstep: misaligned pointer");
   EVAE_REQUIRE(reg_covar >= 0.0, "gmm_mstep: reg_covar=%g", reg_covar);
   const GmLayout w = gm_layout(N, d, K, type);
   char* base = static_cast<char*>(ws);
@@ -739,7 +717,7 @@ extern "C" int evae_gmm_step(const float* x, int N, int d, int K, int type, doub
   hipStream_t stream = (hipStream_t)stream_;
   GM_SIZES("gmm_step");
   EVAE_REQUIRE(x && params && log_resp && logp && state, "gmm_step: null pointer");
-  EVAE_REQUIRE(gm_aligned8(params) && gm_aligned8(log_resp) && gm_aligned8(logp) && gm_aligned8(state), "gmm_step: misaligned pointer");
+  EVAE_REQUIRE(aligned8(params) && aligned8(log_resp) && aligned8(logp) && aligned8(state), "gmm_step: misaligned pointer");
   EVAE_REQUIRE(reg_covar >= 0.0 && tol >= 0.0, "gmm_step: reg_covar=%g, tol=%g", reg_covar, tol);
   const GmLayout w = gm_layout(N, d, K, type);
   char* base = static_cast<char*>(ws);
@@ -753,7 +731,7 @@ extern "C" int evae_gmm_step(const float* x, int N, int d, int K, int type, doub
 
 extern "C" int evae_gmm_prepare(double* params, int d, int K, int type, evae_stream_t stream_) {
   GM_SHAPE("gmm_prepare");
-  EVAE_REQUIRE(params && gm_aligned8(params), "gmm_prepare: null or misaligned params");
+  EVAE_REQUIRE(params && aligned8(params), "gmm_prepare: null or misaligned params");
   gmm_prepare_kernel<<<K, kGmThreads, 0, (hipStream_t)stream_>>>(d, K, type, params);
   return check_launch("gmm_prepare_kernel");
 }
@@ -761,7 +739,7 @@ extern "C" int evae_gmm_prepare(double* params, int d, int K, int type, evae_str
 extern "C" int evae_gmm_argmax(const double* log_resp, int N, int K, int* labels, evae_stream_t stream_) {
   EVAE_REQUIRE(N >= 1 && N <= kGmMaxN, "gmm_argmax: N=%d outside [1, %d]", N, kGmMaxN);
   EVAE_REQUIRE(K >= 1 && K <= kGmMaxK, "gmm_argmax: K=%d outside [1, %d]", K, kGmMaxK);
-  EVAE_REQUIRE(log_resp && labels && gm_aligned8(log_resp), "gmm_argmax: null or misaligned pointer");
+  EVAE_REQUIRE(log_resp && labels && aligned8(log_resp), "gmm_argmax: null or misaligned pointer");
   gmm_argmax_kernel<<<(N + kGmThreads - 1) / kGmThreads, kGmThreads, 0, (hipStream_t)stream_>>>(log_resp, N, K, labels);
   return check_launch("gmm_argmax_kernel");
 }
@@ -771,7 +749,7 @@ extern "C" int evae_gmm_sample(const double* params, int d, int K, int type, con
   GM_SHAPE("gmm_sample");
   EVAE_REQUIRE(n >= 1 && n <= kGmMaxN, "gmm_sample: n=%d outside [1, %d]", n, kGmMaxN);
   EVAE_REQUIRE(params && comp && eps && z, "gmm_sample: null pointer");
-  EVAE_REQUIRE(gm_aligned8(params) && gm_aligned8(eps), "gmm_sample: misaligned params or eps");
+  EVAE_REQUIRE(aligned8(params) && aligned8(eps), "gmm_sample: misaligned params or eps");
   gmm_sample_kernel<<<n, 64, 0, (hipStream_t)stream_>>>(const_cast<double*>(params), d, K, type, comp, eps, n, z);
   return check_launch("gmm_sample_kernel");
 }

@@ -23,7 +23,7 @@
 //   scores:   contingency by int64 atomics; scores in one workgroup (row and column sums, pair counts and the purity as exact
 //             integers; entropies and MI per thread in entry order, then a fixed tree through LDS).
 //   silhouette: x[order] gathered once; per strip evae_pairwise_distance and one wave per row over the clusters' segments.
-#include "evae_common.h"
+#include "evae_latent.h"
 
 namespace evae {
 
@@ -38,21 +38,15 @@ constexpr int kAssignGroups = kKmThreads / kAssignRows;     // 4
 constexpr int kPerThread = kKmTile / kAssignGroups;         // 8 centres of a tile per thread
 constexpr int kOneThreads = 1024;                           // the one-workgroup kernels
 constexpr int kMaxChunks = kKmMaxN / kKmChunk;              // 2048
-constexpr int kNone = 0x7fffffff;
 constexpr int kStateDoubles = 8;
 
 static_assert(kOneThreads >= kKmMaxK, "one thread per cluster in the one-workgroup kernels");
+static_assert(kKmMaxD <= kKmThreads, "pow2_width(d, kKmThreads) is never capped");
 
-__device__ __forceinline__ bool km_done(const double* state) { return state != nullptr && state[1] != 0.0; }
-
-__device__ __forceinline__ int km_wave_sum(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// fixed trees through LDS over the kOneThreads threads of a one-workgroup kernel; the buffer is free again on return
-__device__ __forceinline__ double block_sum(double v, double* buf) {
+// a fixed tree through LDS over the kOneThreads threads of a one-workgroup kernel (double or long long); the buffer is free
+// again on return
+template <typename T>
+__device__ __forceinline__ T block_sum(T v, T* buf) {
   const int tid = threadIdx.x;
   buf[tid] = v;
   __syncthreads();
@@ -60,19 +54,7 @@ __device__ __forceinline__ double block_sum(double v, double* buf) {
     if (tid < s) buf[tid] += buf[tid + s];
     __syncthreads();
   }
-  const double r = buf[0];
-  __syncthreads();
-  return r;
-}
-__device__ __forceinline__ long long block_sum(long long v, long long* buf) {
-  const int tid = threadIdx.x;
-  buf[tid] = v;
-  __syncthreads();
-  for (int s = kOneThreads / 2; s > 0; s >>= 1) {
-    if (tid < s) buf[tid] += buf[tid + s];
-    __syncthreads();
-  }
-  const long long r = buf[0];
+  const T r = buf[0];
   __syncthreads();
   return r;
 }
@@ -84,7 +66,7 @@ __global__ __launch_bounds__(kKmThreads) void kmeans_assign_kernel(const float* 
                                                                    const double* __restrict__ centres, int K, int* labels,
                                                                    double* __restrict__ d2, int* __restrict__ changed,
                                                                    float* __restrict__ dist, const double* state) {
-  if (km_done(state)) return;
+  if (step_done(state)) return;
   extern __shared__ __attribute__((aligned(16))) double km_smem[];
   __shared__ double best_v[kKmThreads];
   __shared__ int best_j[kKmThreads];
@@ -97,7 +79,7 @@ __global__ __launch_bounds__(kKmThreads) void kmeans_assign_kernel(const float* 
     xr[rr * ldx + k] = rr < rows ? x[(size_t)r0 * d + e] : 0.f;
   }
   double bv = INFINITY;
-  int bj = kNone;
+  int bj = kNoIndex;
   const float* xrow = xr + r * ldx;
   for (int t0 = 0; t0 < K; t0 += kKmTile) {
     __syncthreads();                                               // the rows are staged; the last tile has been read
@@ -138,7 +120,7 @@ __global__ __launch_bounds__(kKmThreads) void kmeans_assign_kernel(const float* 
         bj = j;
       }
     }
-    if (bj == kNone) bj = 0;                                       // a row of NaNs
+    if (bj == kNoIndex) bj = 0;                                    // a row of NaNs
     int ch = 0;
     if (r < rows) {
       const int i = r0 + r;
@@ -148,7 +130,7 @@ __global__ __launch_bounds__(kKmThreads) void kmeans_assign_kernel(const float* 
       if (d2) d2[i] = bv;
     }
     if (changed) {
-      ch = km_wave_sum(ch);
+      ch = wave_sum(ch);
       if (r == 0) changed[blockIdx.x] = ch;
     }
   }
@@ -158,7 +140,7 @@ __global__ __launch_bounds__(kKmThreads) void kmeans_assign_kernel(const float* 
 __global__ __launch_bounds__(kKmThreads) void kmeans_hist_kernel(const int* __restrict__ labels, int N, int K,
                                                                  const double* __restrict__ d2, int* __restrict__ hist,
                                                                  double* __restrict__ chunk_sum, const double* state) {
-  if (km_done(state)) return;
+  if (step_done(state)) return;
   __shared__ int h[kKmMaxK];
   __shared__ double wpart[kKmThreads / 64];
   const int tid = threadIdx.x, c0 = blockIdx.x * kKmChunk, c1 = min(N, c0 + kKmChunk);
@@ -172,18 +154,13 @@ __global__ __launch_bounds__(kKmThreads) void kmeans_hist_kernel(const int* __re
   }
   __syncthreads();
   for (int j = tid; j < K; j += kKmThreads) hist[(size_t)blockIdx.x * K + j] = h[j];
-  if (d2) {                                                        // the same in every thread
-    s = wave_sum(s);
-    if ((tid & 63) == 0) wpart[tid >> 6] = s;
-    __syncthreads();
-    if (tid == 0) chunk_sum[blockIdx.x] = ((wpart[0] + wpart[1]) + wpart[2]) + wpart[3];
-  }
+  if (d2) chunk_sum_store(s, wpart, chunk_sum + blockIdx.x);       // the same in every thread
 }
 
 // hist [chunks x K]: counts in, first positions out (cluster-major, then chunk); start [K + 1]
 __global__ __launch_bounds__(kOneThreads) void kmeans_scan_kernel(int* __restrict__ hist, int chunks, int K,
                                                                   int* __restrict__ start, const double* state) {
-  if (km_done(state)) return;
+  if (step_done(state)) return;
   __shared__ int wtot[kOneThreads / 64];
   const int c = threadIdx.x, lane = c & 63, wave = c >> 6;
   int t = 0;
@@ -214,7 +191,7 @@ __global__ __launch_bounds__(kOneThreads) void kmeans_scan_kernel(int* __restric
 __global__ __launch_bounds__(kKmThreads) void kmeans_place_kernel(const int* __restrict__ labels, int N, int K,
                                                                   const int* __restrict__ offs, int* __restrict__ order,
                                                                   const double* state) {
-  if (km_done(state)) return;
+  if (step_done(state)) return;
   constexpr int kOwn = kKmChunk / kKmThreads;
   __shared__ int lab[kKmChunk];
   const int tid = threadIdx.x, c0 = blockIdx.x * kKmChunk, n = min(kKmChunk, N - c0);
@@ -241,7 +218,7 @@ __global__ __launch_bounds__(kKmThreads) void kmeans_place_kernel(const int* __r
 __global__ __launch_bounds__(kKmThreads) void kmeans_segsum_kernel(const float* __restrict__ x, int N, int d, int W, int K,
                                                                    const int* __restrict__ order, const int* __restrict__ start,
                                                                    double* __restrict__ partial, const double* state) {
-  if (km_done(state)) return;
+  if (step_done(state)) return;
   __shared__ double part[kKmThreads];
   const int tid = threadIdx.x, c = tid & (W - 1), g = tid / W, G = kKmThreads / W;
   const int total = min(start[K], N);
@@ -265,20 +242,16 @@ __global__ __launch_bounds__(kKmThreads) void kmeans_segsum_kernel(const float* 
         s += (unsigned)i < (unsigned)N ? (double)x[(size_t)i * d + c] : 0.0;
       }
     }
-    part[tid] = s;
-    __syncthreads();
-    if (g == 0 && c < d) {
-      double t = 0.0;
-      for (int h = 0; h < G; ++h) t += part[h * W + c];
-      partial[((size_t)blockIdx.x + cl) * d + c] = t;
-    }
+    const bool owner = g == 0 && c < d;
+    const double t = group_fold(s, part, c, W, G, owner);
+    if (owner) partial[((size_t)blockIdx.x + cl) * d + c] = t;
     __syncthreads();
   }
 }
 
 __global__ __launch_bounds__(kKmThreads) void kmeans_sums_kernel(const double* __restrict__ partial, const int* __restrict__ start,
                                                                  int K, int d, double* __restrict__ sums, const double* state) {
-  if (km_done(state)) return;
+  if (step_done(state)) return;
   const int idx = blockIdx.x * kKmThreads + threadIdx.x;
   if (idx >= K * d) return;
   const int cl = idx / d, c = idx - cl * d;
@@ -296,7 +269,7 @@ __global__ __launch_bounds__(kOneThreads) void kmeans_finish_kernel(const float*
                                                                     const int* __restrict__ changed, int nchanged,
                                                                     const double* __restrict__ chunk_sum, int chunks,
                                                                     double tol_abs, double* state) {
-  if (km_done(state)) return;
+  if (step_done(state)) return;
   __shared__ int cnt[kKmMaxK];
   __shared__ int taken_i[kKmMaxK];
   __shared__ double taken_v[kKmMaxK];
@@ -314,7 +287,7 @@ __global__ __launch_bounds__(kOneThreads) void kmeans_finish_kernel(const float*
   for (int e = 0; e < K; ++e) {
     if (cnt[e] != 0) continue;                                     // LDS, behind a barrier: the same in every thread
     double bv = -1.0;
-    int bi = kNone;
+    int bi = kNoIndex;
     for (int i = tid; i < N; i += kOneThreads) {                   // ascending i, ">": the lowest index of the largest d2
       const double v = d2[i];
       if (v > bv) {
@@ -342,7 +315,7 @@ __global__ __launch_bounds__(kOneThreads) void kmeans_finish_kernel(const float*
     const int pick = red_i[0];
     const double pv = red_v[0];
     __syncthreads();
-    if (pick == kNone) continue;                                   // no donor (cannot happen while K <= N)
+    if (pick == kNoIndex) continue;                                   // no donor (cannot happen while K <= N)
     const int donor = labels[pick];
     for (int c = tid; c < d; c += kOneThreads) {
       const double xv = (double)x[(size_t)pick * d + c];
@@ -374,16 +347,7 @@ __global__ __launch_bounds__(kOneThreads) void kmeans_finish_kernel(const float*
   }
   const double shift = block_sum(sh, red_v);
 
-  double inertia = 0.0;                                            // the chunk sums in chunk order, by one thread out of LDS
-  for (int c0 = 0; c0 < chunks; c0 += kOneThreads) {
-    if (c0 + tid < chunks) red_v[tid] = chunk_sum[c0 + tid];
-    __syncthreads();
-    if (tid == 0) {
-      const int n = min(kOneThreads, chunks - c0);
-      for (int e = 0; e < n; ++e) inertia += red_v[e];
-    }
-    __syncthreads();
-  }
+  const double inertia = ordered_total<kOneThreads>(chunk_sum, chunks, red_v);   // thread 0's
   if (tid == 0) {
     const double it = state[0] + 1.0;
     const bool done = (it > 1.0 && n_changed == 0) || shift <= tol_abs;
@@ -405,27 +369,14 @@ __global__ __launch_bounds__(kKmThreads) void kmeans_chunk_sum_kernel(const doub
   const int tid = threadIdx.x, c0 = blockIdx.x * kKmChunk, c1 = min(N, c0 + kKmChunk);
   double s = 0.0;
   for (int i = c0 + tid; i < c1; i += kKmThreads) s += d2[i];
-  s = wave_sum(s);
-  if ((tid & 63) == 0) wpart[tid >> 6] = s;
-  __syncthreads();
-  if (tid == 0) chunk_sum[blockIdx.x] = ((wpart[0] + wpart[1]) + wpart[2]) + wpart[3];
+  chunk_sum_store(s, wpart, chunk_sum + blockIdx.x);
 }
 
 __global__ __launch_bounds__(kOneThreads) void kmeans_total_kernel(const double* __restrict__ chunk_sum, int chunks,
                                                                    double* __restrict__ out) {
   __shared__ double buf[kOneThreads];
-  const int tid = threadIdx.x;
-  double total = 0.0;
-  for (int c0 = 0; c0 < chunks; c0 += kOneThreads) {
-    if (c0 + tid < chunks) buf[tid] = chunk_sum[c0 + tid];
-    __syncthreads();
-    if (tid == 0) {
-      const int n = min(kOneThreads, chunks - c0);
-      for (int e = 0; e < n; ++e) total += buf[e];
-    }
-    __syncthreads();
-  }
-  if (tid == 0) out[0] = total;
+  const double total = ordered_total<kOneThreads>(chunk_sum, chunks, buf);
+  if (threadIdx.x == 0) out[0] = total;
 }
 
 // ---------------------------------------------------------------- seed
@@ -482,8 +433,8 @@ __global__ __launch_bounds__(kOneThreads) void kmeans_seed_pick_kernel(const flo
   const int tid = threadIdx.x;
   for (int ch = tid; ch < chunks; ch += kOneThreads) base[ch + 1] = totals[ch];
   if (tid == 0) {
-    chunk_s = kNone;
-    pick_s = kNone;
+    chunk_s = kNoIndex;
+    pick_s = kNoIndex;
   }
   __syncthreads();
   if (tid == 0) {
@@ -504,13 +455,13 @@ __global__ __launch_bounds__(kOneThreads) void kmeans_seed_pick_kernel(const flo
       if (base[ch + 1] > target) atomicMin(&chunk_s, ch);          // base[ch + 1] == base[ch] + the chunk's last running sum
     __syncthreads();
     const int ch = chunk_s;
-    if (ch != kNone) {
+    if (ch != kNoIndex) {
       const int c0 = ch * kKmChunk, n = min(kKmChunk, N - c0);
       for (int e = tid; e < n; e += kOneThreads)
         if (base[ch] + prefix[c0 + e] > target) atomicMin(&pick_s, c0 + e);
     }
     __syncthreads();
-    pick = pick_s == kNone ? N - 1 : pick_s;
+    pick = pick_s == kNoIndex ? N - 1 : pick_s;
   } else {                                                         // fewer distinct points than centres: the lowest unused index
     for (int j = tid; j <= t && j < N; j += kOneThreads) {
       bool used = false;
@@ -518,7 +469,7 @@ __global__ __launch_bounds__(kOneThreads) void kmeans_seed_pick_kernel(const flo
       if (!used) atomicMin(&pick_s, j);
     }
     __syncthreads();
-    pick = pick_s == kNone ? N - 1 : pick_s;
+    pick = pick_s == kNoIndex ? N - 1 : pick_s;
   }
   __syncthreads();
   if (tid == 0) idx[t] = pick;
@@ -655,22 +606,17 @@ static int km_blocks(int N) { return (N + kAssignRows - 1) / kAssignRows; }
 
 static KmLayout km_layout(int N, int d, int K) {
   KmLayout w;
-  size_t o = 0;
-  auto take = [&o](size_t bytes) {
-    const size_t at = o;
-    o += align_up(bytes, 256);
-    return at;
-  };
+  WsCursor ws;
   const size_t chunks = (size_t)km_chunks(N);
-  w.partial = take((chunks + K) * d * sizeof(double));
-  w.sums = take((size_t)K * d * sizeof(double));
-  w.chunk_sum = take(chunks * sizeof(double));
-  w.d2min = take((size_t)N * sizeof(double));
-  w.prefix = take((size_t)N * sizeof(double));
-  w.totals = take(chunks * sizeof(double));
-  w.hist = take(chunks * K * sizeof(int));
-  w.changed = take((size_t)km_blocks(N) * sizeof(int));
-  w.bytes = o;
+  w.partial = ws.take((chunks + K) * d * sizeof(double));
+  w.sums = ws.take((size_t)K * d * sizeof(double));
+  w.chunk_sum = ws.take(chunks * sizeof(double));
+  w.d2min = ws.take((size_t)N * sizeof(double));
+  w.prefix = ws.take((size_t)N * sizeof(double));
+  w.totals = ws.take(chunks * sizeof(double));
+  w.hist = ws.take(chunks * K * sizeof(int));
+  w.changed = ws.take((size_t)km_blocks(N) * sizeof(int));
+  w.bytes = ws.o;
   return w;
 }
 
@@ -679,13 +625,9 @@ static int km_assign_launch(const float* x, int N, int d, const double* centres,
   constexpr int kMaxLds = kKmTile * kKmMaxD * (int)sizeof(double) + kAssignRows * (kKmMaxD | 1) * (int)sizeof(float);
   static_assert(kMaxLds + kKmThreads * 12 <= 160 * 1024, "a tile of centres and a block's rows fit the workgroup's LDS at d = 256");
   // Only a wide input (d > 64) needs more LDS than a launch gets unasked: the latents' d = 40 iterates without this host call.
-  // Where it is needed, at every call, not once per process: the attribute belongs to the function on the CURRENT device.
   if (assign_lds_bytes(d) > 32 * 1024) {
-    const hipError_t e = hipFuncSetAttribute((const void*)kmeans_assign_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds);
-    if (e != hipSuccess) {
-      set_error("kmeans_assign: %d bytes of LDS refused: %s", kMaxLds, hipGetErrorString(e));
-      return EVAE_ELAUNCH;
-    }
+    const int rc = set_max_lds((const void*)kmeans_assign_kernel, kMaxLds, "kmeans_assign");
+    if (rc) return rc;
   }
   kmeans_assign_kernel<<<km_blocks(N), kKmThreads, assign_lds_bytes(d), stream>>>(x, N, d, centres, K, labels, d2, changed, dist,
                                                                                   state);
@@ -698,8 +640,7 @@ static int km_update_launch(const float* x, int N, int d, const int* labels, int
   const int chunks = km_chunks(N);
   int* hist = reinterpret_cast<int*>(ws + w.hist);
   double* partial = reinterpret_cast<double*>(ws + w.partial);
-  int W = 1;
-  while (W < d) W <<= 1;
+  const int W = pow2_width(d, kKmThreads);
   kmeans_hist_kernel<<<chunks, kKmThreads, 0, stream>>>(labels, N, K, d2, hist, reinterpret_cast<double*>(ws + w.chunk_sum), state);
   int rc = check_launch("kmeans_hist_kernel");
   if (rc) return rc;
@@ -712,8 +653,6 @@ static int km_update_launch(const float* x, int N, int d, const int* labels, int
   kmeans_sums_kernel<<<(K * d + kKmThreads - 1) / kKmThreads, kKmThreads, 0, stream>>>(partial, start, K, d, sums, state);
   return check_launch("kmeans_sums_kernel");
 }
-
-static bool km_aligned8(const void* p) { return ((uintptr_t)p & 7) == 0; }
 
 }  // namespace evae
 
@@ -744,14 +683,14 @@ extern "C" int evae_kmeans_assign(const float* x, int N, int d, const double* ce
                                   evae_stream_t stream_) {
   KM_SIZES("kmeans_assign");
   EVAE_REQUIRE(x && centres && labels && d2, "kmeans_assign: null pointer");
-  EVAE_REQUIRE(km_aligned8(centres) && km_aligned8(d2), "kmeans_assign: misaligned centres or d2");
+  EVAE_REQUIRE(aligned8(centres) && aligned8(d2), "kmeans_assign: misaligned centres or d2");
   return km_assign_launch(x, N, d, centres, K, labels, d2, nullptr, nullptr, nullptr, (hipStream_t)stream_);
 }
 
 extern "C" int evae_kmeans_transform(const float* x, int N, int d, const double* centres, int K, float* out, evae_stream_t stream_) {
   KM_SIZES("kmeans_transform");
   EVAE_REQUIRE(x && centres && out, "kmeans_transform: null pointer");
-  EVAE_REQUIRE(km_aligned8(centres), "kmeans_transform: misaligned centres");
+  EVAE_REQUIRE(aligned8(centres), "kmeans_transform: misaligned centres");
   return km_assign_launch(x, N, d, centres, K, nullptr, nullptr, nullptr, out, nullptr, (hipStream_t)stream_);
 }
 
@@ -759,7 +698,7 @@ extern "C" int evae_kmeans_update(const float* x, int N, int d, const int* label
                                   void* ws, size_t ws_bytes, evae_stream_t stream_) {
   KM_SIZES("kmeans_update");
   EVAE_REQUIRE(x && labels && order && start && sums, "kmeans_update: null pointer");
-  EVAE_REQUIRE(km_aligned8(sums), "kmeans_update: misaligned sums");
+  EVAE_REQUIRE(aligned8(sums), "kmeans_update: misaligned sums");
   KM_WORKSPACE("kmeans_update");
   return km_update_launch(x, N, d, labels, K, nullptr, order, start, sums, static_cast<char*>(ws), km_layout(N, d, K), nullptr,
                           (hipStream_t)stream_);
@@ -771,7 +710,7 @@ extern "C" int evae_kmeans_step(const float* x, int N, int d, int K, double* cen
   KM_SIZES("kmeans_step");
   EVAE_REQUIRE(K <= N, "kmeans_step: K=%d centres for N=%d points", K, N);
   EVAE_REQUIRE(x && centres && labels && d2 && order && start && state, "kmeans_step: null pointer");
-  EVAE_REQUIRE(km_aligned8(centres) && km_aligned8(d2) && km_aligned8(state), "kmeans_step: misaligned centres, d2 or state");
+  EVAE_REQUIRE(aligned8(centres) && aligned8(d2) && aligned8(state), "kmeans_step: misaligned centres, d2 or state");
   EVAE_REQUIRE(tol_abs >= 0.0, "kmeans_step: tol_abs=%g", tol_abs);
   KM_WORKSPACE("kmeans_step");
   const KmLayout w = km_layout(N, d, K);
@@ -793,7 +732,7 @@ extern "C" int evae_kmeans_seed(const float* x, int N, int d, int K, const doubl
   KM_SIZES("kmeans_seed");
   EVAE_REQUIRE(K <= N, "kmeans_seed: K=%d centres for N=%d points", K, N);
   EVAE_REQUIRE(x && u && idx && centres, "kmeans_seed: null pointer");
-  EVAE_REQUIRE(km_aligned8(u) && km_aligned8(centres), "kmeans_seed: misaligned u or centres");
+  EVAE_REQUIRE(aligned8(u) && aligned8(centres), "kmeans_seed: misaligned u or centres");
   KM_WORKSPACE("kmeans_seed");
   const KmLayout w = km_layout(N, d, K);
   char* base = static_cast<char*>(ws);
@@ -816,7 +755,7 @@ extern "C" int evae_kmeans_inertia(const double* d2, int N, double* out, void* w
   hipStream_t stream = (hipStream_t)stream_;
   EVAE_REQUIRE(N >= 1 && N <= kKmMaxN, "kmeans_inertia: N=%d outside [1, %d]", N, kKmMaxN);
   EVAE_REQUIRE(d2 && out && ws, "kmeans_inertia: null pointer");
-  EVAE_REQUIRE(km_aligned8(d2) && km_aligned8(out) && km_aligned8(ws), "kmeans_inertia: misaligned pointer");
+  EVAE_REQUIRE(aligned8(d2) && aligned8(out) && aligned8(ws), "kmeans_inertia: misaligned pointer");
   const int chunks = km_chunks(N);
   EVAE_REQUIRE(ws_bytes >= (size_t)chunks * sizeof(double), "kmeans_inertia: workspace of %zu bytes, %zu needed", ws_bytes,
                (size_t)chunks * sizeof(double));
@@ -834,7 +773,7 @@ extern "C" int evae_cluster_contingency(const int* a, int Ka, const int* b, int 
   EVAE_REQUIRE(N >= 1 && N <= kKmMaxN, "cluster_contingency: N=%d outside [1, %d]", N, kKmMaxN);
   EVAE_REQUIRE(Ka >= 1 && Ka <= kKmMaxK && Kb >= 1 && Kb <= kKmMaxK, "cluster_contingency: %d x %d outside [1, %d]^2", Ka, Kb,
                kKmMaxK);
-  EVAE_REQUIRE(a && b && table && km_aligned8(table), "cluster_contingency: null or misaligned pointer");
+  EVAE_REQUIRE(a && b && table && aligned8(table), "cluster_contingency: null or misaligned pointer");
   const hipError_t e = hipMemsetAsync(table, 0, (size_t)Ka * Kb * sizeof(long long), stream);
   if (e != hipSuccess) {
     set_error("cluster_contingency: clearing the table: %s", hipGetErrorString(e));
@@ -847,7 +786,7 @@ extern "C" int evae_cluster_contingency(const int* a, int Ka, const int* b, int 
 
 extern "C" int evae_cluster_scores(const long long* table, int Ka, int Kb, double* out, evae_stream_t stream_) {
   EVAE_REQUIRE(Ka >= 1 && Ka <= kKmMaxK && Kb >= 1 && Kb <= kKmMaxK, "cluster_scores: %d x %d outside [1, %d]^2", Ka, Kb, kKmMaxK);
-  EVAE_REQUIRE(table && out && km_aligned8(table) && km_aligned8(out), "cluster_scores: null or misaligned pointer");
+  EVAE_REQUIRE(table && out && aligned8(table) && aligned8(out), "cluster_scores: null or misaligned pointer");
   cluster_scores_kernel<<<1, kOneThreads, 0, (hipStream_t)stream_>>>(table, Ka, Kb, out);
   return check_launch("cluster_scores_kernel");
 }
@@ -868,10 +807,10 @@ extern "C" int evae_silhouette_samples(const float* x, int N, int d, const int* 
   EVAE_REQUIRE(K >= 1 && K <= N, "silhouette_samples: K=%d outside [1, N = %d]", K, N);
   EVAE_REQUIRE(strip_rows >= 0, "silhouette_samples: strip_rows=%d (0 = automatic)", strip_rows);
   EVAE_REQUIRE(x && order && start && out && ws, "silhouette_samples: null pointer");
-  EVAE_REQUIRE(km_aligned8(out) && ((uintptr_t)ws & 255) == 0, "silhouette_samples: misaligned out or workspace");
+  EVAE_REQUIRE(aligned8(out) && ((uintptr_t)ws & 255) == 0, "silhouette_samples: misaligned out or workspace");
   EVAE_REQUIRE(ws_bytes >= evae_silhouette_workspace_bytes(N, d, strip_rows), "silhouette_samples: workspace of %zu bytes, %zu needed",
                ws_bytes, evae_silhouette_workspace_bytes(N, d, strip_rows));
-  const int R = (int)(evae_tsne_knn_workspace_bytes(N, strip_rows) / ((size_t)N * sizeof(float)));
+  const int R = strip_rows_of(N, strip_rows);
   float* xs = static_cast<float*>(ws);
   float* strip = reinterpret_cast<float*>(static_cast<char*>(ws) + silhouette_rows_bytes(N, d));
   const size_t items = (size_t)N * d;
@@ -879,12 +818,9 @@ extern "C" int evae_silhouette_samples(const float* x, int N, int d, const int* 
   int rc = check_launch("silhouette_gather_kernel");
   if (rc) return rc;
   constexpr int kRowsPerBlock = kKmThreads / 64;
-  for (int r0 = 0; r0 < N; r0 += R) {
-    const int rows = N - r0 < R ? N - r0 : R;
-    if ((rc = evae_pairwise_distance(xs + (size_t)r0 * d, rows, xs, N, d, strip, stream_))) return rc;
+  return for_each_strip(xs, N, d, R, strip, stream_, [&](int r0, int rows) {
     silhouette_reduce_kernel<<<(rows + kRowsPerBlock - 1) / kRowsPerBlock, kKmThreads, 0, stream>>>(strip, N, r0, rows, order, start,
                                                                                                      K, out);
-    if ((rc = check_launch("silhouette_reduce_kernel"))) return rc;
-  }
-  return EVAE_OK;
+    return check_launch("silhouette_reduce_kernel");
+  });
 }

@@ -14,7 +14,7 @@
 //              near neighbours -- leaves after one comparison.  An inclusive prefix sum of the bins gives, for the t-th sorted
 //              threshold, the number of elements below it; the sort permutation is undone on the way out.  Integer LDS atomics
 //              only: counts do not depend on order.  An entry j == i or outside [0, N) is never dereferenced and gets rank 0.
-#include "evae_common.h"
+#include "evae_latent.h"
 
 namespace evae {
 
@@ -22,12 +22,6 @@ constexpr int kRankThreads = 256;
 constexpr int kRankMaxK = 256;            // = evae_tsne_nn_max_neighbours(): one lane of wave 0 scans 4 bins
 constexpr int kBinCopies = 16;
 constexpr unsigned long long kNoThreshold = ~0ull;
-
-__device__ __forceinline__ int wave_sum_int(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // sorted[0 .. kv): ascending, distinct or equal only between repeated columns; top = sorted[kv - 1] (0 when kv == 0).
 // (key, l) is counted for every threshold above it: bin p = the number of thresholds <= (key, l), nothing to do at p == kv.
@@ -136,8 +130,8 @@ __global__ __launch_bounds__(kRankThreads) void nn_rank_count_kernel(const float
     penalty = r > k ? r - k : 0;
     hit = r >= 1 && r <= k;
   }
-  penalty = wave_sum_int(penalty);
-  hit = wave_sum_int(hit);
+  penalty = wave_sum(penalty);
+  hit = wave_sum(hit);
   if (lane == 0) {
     wsum[2 * wave] = penalty;
     wsum[2 * wave + 1] = hit;
@@ -149,11 +143,6 @@ __global__ __launch_bounds__(kRankThreads) void nn_rank_count_kernel(const float
     for (int w = 0; w < kRankThreads / 64; ++w) s += wsum[2 * w + tid];
     sums[(size_t)blockIdx.x * 2 + tid] = s;
   }
-}
-
-// the strip of the neighbour search, by its own rule: R rows of N distances
-static int rank_strip_rows(int N, int strip_rows) {
-  return (int)(evae_tsne_knn_workspace_bytes(N, strip_rows) / ((size_t)N * sizeof(float)));
 }
 
 }  // namespace evae
@@ -177,18 +166,13 @@ extern "C" int evae_nn_rank(const float* z, int N, int zdim, const int* nbr, int
   EVAE_REQUIRE(strip_rows >= 0, "nn_rank: strip_rows=%d (0 = automatic)", strip_rows);
   EVAE_REQUIRE(z && nbr && rank && row_sums && ws, "nn_rank: null pointer");
   EVAE_REQUIRE(((uintptr_t)ws & 3) == 0 && ((uintptr_t)row_sums & 7) == 0, "nn_rank: misaligned workspace or row_sums");
-  const int R = rank_strip_rows(N, strip_rows);
+  const int R = strip_rows_of(N, strip_rows);               // the strip of the neighbour search, by its own rule
   EVAE_REQUIRE(ws_bytes >= (size_t)R * (size_t)N * sizeof(float), "nn_rank: workspace of %zu bytes, %zu needed", ws_bytes,
                (size_t)R * (size_t)N * sizeof(float));
   float* strip = static_cast<float*>(ws);
-  for (int r0 = 0; r0 < N; r0 += R) {
-    const int rows = N - r0 < R ? N - r0 : R;
-    int rc = evae_pairwise_distance(z + (size_t)r0 * zdim, rows, z, N, zdim, strip, stream_);
-    if (rc) return rc;
+  return for_each_strip(z, N, zdim, R, strip, stream_, [&](int r0, int rows) {
     nn_rank_count_kernel<<<rows, kRankThreads, 0, stream>>>(strip, N, r0, k, nbr + (size_t)r0 * k, rank + (size_t)r0 * k,
                                                             row_sums + (size_t)r0 * 2);
-    rc = check_launch("nn_rank_count_kernel");
-    if (rc) return rc;
-  }
-  return EVAE_OK;
+    return check_launch("nn_rank_count_kernel");
+  });
 }

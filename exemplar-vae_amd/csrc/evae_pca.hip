@@ -13,7 +13,7 @@
 //             G and V sit in LDS for d <= kLdsMaxD and in the caller's workspace above; the code is the same (a template flag
 //             picks the pointer).
 //   project / reconstruct: 16 rows per block, staged in LDS as doubles; a thread owns (row, output column) items.
-#include "evae_common.h"
+#include "evae_latent.h"
 
 namespace evae {
 
@@ -32,12 +32,6 @@ constexpr int kEighMaxWaves = 16;
 constexpr int kPerLane = kPcaMaxD / 64;      // entries of a column per lane of the wave that owns it
 constexpr double kEps = 2.220446049250313e-16;   // 2^-52
 
-__device__ __forceinline__ int wave_sum_i32(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // ---------------------------------------------------------------- moments
 // sums [chunks x d]: thread (g, c) adds rows g, g + G, .. of its chunk in column c; the G partial sums are added in order of g.
 __global__ __launch_bounds__(kPcaThreads) void pca_colsum_kernel(const float* __restrict__ x, int N, int d, int W,
@@ -48,13 +42,9 @@ __global__ __launch_bounds__(kPcaThreads) void pca_colsum_kernel(const float* __
   double s = 0.0;
   if (c < d)
     for (int r = r0 + g; r < r1; r += G) s += (double)x[(size_t)r * d + c];
-  part[tid] = s;
-  __syncthreads();
-  if (g == 0 && c < d) {
-    double t = 0.0;
-    for (int h = 0; h < G; ++h) t += part[h * W + c];
-    sums[(size_t)blockIdx.x * d + c] = t;
-  }
+  const bool owner = g == 0 && c < d;
+  const double t = group_fold(s, part, c, W, G, owner);
+  if (owner) sums[(size_t)blockIdx.x * d + c] = t;
 }
 
 __global__ __launch_bounds__(kPcaThreads) void pca_mean_kernel(const double* __restrict__ sums, int chunks, int N, int d,
@@ -232,10 +222,10 @@ __global__ __launch_bounds__(64 * kEighMaxWaves) void pca_eigh_kernel(const doub
     const double lj = lam[j];
     int before = 0;
     for (int k = lane; k < d; k += 64) before += (lam[k] > lj) || (lam[k] == lj && k < j);
-    const int place = wave_sum_i32(before);
+    const int place = wave_sum(before);
     const double* v = V + j * d;
     double best = -1.0;
-    int where = 0x7fffffff;
+    int where = kNoIndex;
     for (int i = lane; i < d; i += 64) {
       const double a = fabs(v[i]);
       if (a > best) {
@@ -327,16 +317,13 @@ extern "C" int evae_pca_moments(const float* x, int N, int d, double* mean, doub
   EVAE_REQUIRE(d >= 1 && d <= kPcaMaxD, "pca_moments: d=%d outside [1, %d]", d, kPcaMaxD);
   EVAE_REQUIRE(N >= 2 && N <= kPcaMaxN, "pca_moments: N=%d outside [2, %d]", N, kPcaMaxN);
   EVAE_REQUIRE(x && mean && cov && ws, "pca_moments: null pointer");
-  EVAE_REQUIRE(((uintptr_t)ws & 7) == 0 && ((uintptr_t)mean & 7) == 0 && ((uintptr_t)cov & 7) == 0,
-               "pca_moments: misaligned workspace, mean or cov");
+  EVAE_REQUIRE(aligned8(ws) && aligned8(mean) && aligned8(cov), "pca_moments: misaligned workspace, mean or cov");
   EVAE_REQUIRE(ws_bytes >= evae_pca_workspace_bytes(N, d), "pca_moments: workspace of %zu bytes, %zu needed", ws_bytes,
                evae_pca_workspace_bytes(N, d));
   const int chunks = pca_chunks(N), T = (d + kTile - 1) / kTile;
   double* sums = static_cast<double*>(ws);
   double* gram = sums + (size_t)chunks * d;
-  int W = 1;
-  while (W < d) W <<= 1;
-  pca_colsum_kernel<<<chunks, kPcaThreads, 0, stream>>>(x, N, d, W, sums);
+  pca_colsum_kernel<<<chunks, kPcaThreads, 0, stream>>>(x, N, d, pow2_width(d, kPcaThreads), sums);
   int rc = check_launch("pca_colsum_kernel");
   if (rc) return rc;
   pca_mean_kernel<<<1, kPcaThreads, 0, stream>>>(sums, chunks, N, d, mean);
@@ -354,18 +341,13 @@ extern "C" int evae_pca_eigh(const double* cov, int d, double* evals, double* ev
   hipStream_t stream = (hipStream_t)stream_;
   EVAE_REQUIRE(d >= 1 && d <= kPcaMaxD, "pca_eigh: d=%d outside [1, %d]", d, kPcaMaxD);
   EVAE_REQUIRE(cov && evals && evecs && info, "pca_eigh: null pointer");
-  EVAE_REQUIRE((((uintptr_t)cov | (uintptr_t)evals | (uintptr_t)evecs | (uintptr_t)info | (uintptr_t)ws) & 7) == 0,
+  EVAE_REQUIRE(aligned8(cov) && aligned8(evals) && aligned8(evecs) && aligned8(info) && aligned8(ws),
                "pca_eigh: misaligned pointer");
   int waves = (d + 1) / 2;
   waves = waves < 1 ? 1 : (waves > kEighMaxWaves ? kEighMaxWaves : waves);
   if (d <= kLdsMaxD) {
-    // at every call, not once per process: the attribute belongs to the function on the CURRENT device
-    const hipError_t e = hipFuncSetAttribute((const void*)pca_eigh_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             2 * kLdsMaxD * kLdsMaxD * (int)sizeof(double));
-    if (e != hipSuccess) {
-      set_error("pca_eigh: %d bytes of LDS refused: %s", 2 * kLdsMaxD * kLdsMaxD * (int)sizeof(double), hipGetErrorString(e));
-      return EVAE_ELAUNCH;
-    }
+    const int rc = set_max_lds((const void*)pca_eigh_kernel<true>, 2 * kLdsMaxD * kLdsMaxD * (int)sizeof(double), "pca_eigh");
+    if (rc) return rc;
     pca_eigh_kernel<true><<<1, 64 * waves, 2 * (size_t)d * d * sizeof(double), stream>>>(cov, d, evals, evecs, info, nullptr);
   } else {
     EVAE_REQUIRE(ws && ws_bytes >= evae_pca_eigh_workspace_bytes(d), "pca_eigh: workspace of %zu bytes, %zu needed", ws_bytes,
@@ -381,7 +363,7 @@ extern "C" int evae_pca_project(const float* x, int N, int d, const double* mean
   EVAE_REQUIRE(N >= 1 && N <= kPcaMaxN, "pca_project: N=%d outside [1, %d]", N, kPcaMaxN);
   EVAE_REQUIRE(k >= 1 && k <= d, "pca_project: k=%d outside [1, d = %d]", k, d);
   EVAE_REQUIRE(x && mean && W && out, "pca_project: null pointer");
-  EVAE_REQUIRE((((uintptr_t)mean | (uintptr_t)W) & 7) == 0, "pca_project: misaligned mean or W");
+  EVAE_REQUIRE(aligned8(mean) && aligned8(W), "pca_project: misaligned mean or W");
   pca_project_kernel<<<(N + kRowsPerBlock - 1) / kRowsPerBlock, kPcaThreads, 0, (hipStream_t)stream_>>>(x, N, d, mean, W, k,
                                                                                                        scale, out);
   return check_launch("pca_project_kernel");
@@ -393,7 +375,7 @@ extern "C" int evae_pca_reconstruct(const float* y, int N, int k, const double* 
   EVAE_REQUIRE(N >= 1 && N <= kPcaMaxN, "pca_reconstruct: N=%d outside [1, %d]", N, kPcaMaxN);
   EVAE_REQUIRE(k >= 1 && k <= d, "pca_reconstruct: k=%d outside [1, d = %d]", k, d);
   EVAE_REQUIRE(y && mean && W && out, "pca_reconstruct: null pointer");
-  EVAE_REQUIRE((((uintptr_t)mean | (uintptr_t)W) & 7) == 0, "pca_reconstruct: misaligned mean or W");
+  EVAE_REQUIRE(aligned8(mean) && aligned8(W), "pca_reconstruct: misaligned mean or W");
   pca_reconstruct_kernel<<<(N + kRowsPerBlock - 1) / kRowsPerBlock, kPcaThreads, 0, (hipStream_t)stream_>>>(y, N, k, mean, W, d,
                                                                                                            out);
   return check_launch("pca_reconstruct_kernel");

@@ -17,13 +17,12 @@
 //                 to rep[cs][i][3].  Launch 2, attraction: a wave per CSR row loops over its non-zeros, then adds the row's
 //                 column-split partials in split order and writes the [8] record of evae_tsne_forces.  Fixed order throughout,
 //                 no floating-point atomics, no grid-wide barrier.  Launch 3 is evae_tsne_update.
-#include "evae_common.h"
+#include "evae_latent.h"
 
 namespace evae {
 
 constexpr int kNnMaxPoints = 131072;      // see include/evae_hip.h for what sets it
 constexpr int kNnMaxNeighbours = 256;     // one wave holds a row of the search in registers, 4 values per lane
-constexpr size_t kNnStripBytes = (size_t)256 << 20;
 constexpr int kSelThreads = 256;
 constexpr int kHistCopies = 16;           // the top byte of a float puts most of a row into a few bins: 16 copies, one per lane & 15
 constexpr int kRepRows = 256;             // rows of a repulsion block = its threads
@@ -302,13 +301,6 @@ static void rep_split(int N, int* splits, int* tiles_per_split) {
   *splits = cdiv(tiles, *tiles_per_split);
 }
 
-static int strip_rows_auto(int N) {
-  size_t r = kNnStripBytes / ((size_t)N * sizeof(float));
-  if (r >= 64) r &= ~(size_t)63;                              // whole tiles of the distance kernel
-  if (r < 1) r = 1;
-  return r > (size_t)N ? N : (int)r;
-}
-
 }  // namespace evae
 
 using namespace evae;
@@ -318,8 +310,7 @@ extern "C" int evae_tsne_nn_max_neighbours(void) { return kNnMaxNeighbours; }
 
 extern "C" size_t evae_tsne_knn_workspace_bytes(int N, int strip_rows) {
   if (N < 1) return 0;
-  const int R = strip_rows > 0 ? (strip_rows > N ? N : strip_rows) : strip_rows_auto(N);
-  return (size_t)R * (size_t)N * sizeof(float);
+  return (size_t)strip_rows_of(N, strip_rows) * (size_t)N * sizeof(float);
 }
 
 extern "C" int evae_tsne_knn(const float* z, int N, int zdim, int k, int strip_rows, int* idx, float* d2, void* ws, size_t ws_bytes,
@@ -331,19 +322,14 @@ extern "C" int evae_tsne_knn(const float* z, int N, int zdim, int k, int strip_r
   EVAE_REQUIRE(k <= N - 1, "tsne_knn: k=%d but a point has only N - 1 = %d neighbours", k, N - 1);
   EVAE_REQUIRE(strip_rows >= 0, "tsne_knn: strip_rows=%d (0 = automatic)", strip_rows);
   EVAE_REQUIRE(z && idx && d2 && ws, "tsne_knn: null pointer");
-  const int R = strip_rows > 0 ? (strip_rows > N ? N : strip_rows) : strip_rows_auto(N);
+  const int R = strip_rows_of(N, strip_rows);
   EVAE_REQUIRE(ws_bytes >= (size_t)R * (size_t)N * sizeof(float), "tsne_knn: workspace of %zu bytes, %zu needed", ws_bytes,
                (size_t)R * (size_t)N * sizeof(float));
   float* strip = static_cast<float*>(ws);
-  for (int r0 = 0; r0 < N; r0 += R) {
-    const int rows = N - r0 < R ? N - r0 : R;
-    int rc = evae_pairwise_distance(z + (size_t)r0 * zdim, rows, z, N, zdim, strip, stream_);
-    if (rc) return rc;
+  return for_each_strip(z, N, zdim, R, strip, stream_, [&](int r0, int rows) {
     tsne_knn_select_kernel<<<rows, kSelThreads, 0, stream>>>(strip, N, r0, k, idx + (size_t)r0 * k, d2 + (size_t)r0 * k);
-    rc = check_launch("tsne_knn_select_kernel");
-    if (rc) return rc;
-  }
-  return EVAE_OK;
+    return check_launch("tsne_knn_select_kernel");
+  });
 }
 
 extern "C" int evae_tsne_nn_conditionals(const float* d2, int N, int k, double perplexity, int steps, float* beta, float* cond,

@@ -20,23 +20,8 @@ import numpy as np
 import torch
 
 from . import ops
+from ._fit import _blind_batches, _generator, _int_at_least, _rows, _shape
 from ._lib import EvaeError
-
-
-def _rows(X, device):
-    """tensor or array -> contiguous float32 tensor on the device (an array or a host tensor goes to `device`, default cuda: the
-    same data is taken the same way whichever of the three it comes as)"""
-    if not torch.is_tensor(X):
-        X = torch.as_tensor(np.ascontiguousarray(np.asarray(X, dtype=np.float32)), device=device or 'cuda')
-    elif not X.is_cuda:
-        X = X.to(device or 'cuda')
-    if X.dtype != torch.float32:
-        X = X.float()
-    return X if X.is_contiguous() else X.contiguous()
-
-
-def _shape(X):
-    return tuple(X.shape) if torch.is_tensor(X) else np.shape(X)
 
 
 class KMeans:
@@ -47,8 +32,7 @@ class KMeans:
         tol: relative to the mean population variance of the features, as scikit-learn's.  random_state seeds a CPU
         torch.Generator all uniforms (float64) and row choices come from; None draws a seed.  check_every: iterations issued
         between two reads of the device's record.  device: where a host array given to fit goes (default cuda)."""
-        if isinstance(n_clusters, bool) or not isinstance(n_clusters, (int, np.integer)) or n_clusters < 1:
-            raise ValueError("KMeans: n_clusters=%r; an int >= 1 expected" % (n_clusters,))
+        n_clusters = _int_at_least("KMeans", "n_clusters", n_clusters, 1)
         if isinstance(init, str):
             if init not in ('k-means++', 'random'):
                 raise ValueError("KMeans: init=%r; 'k-means++', 'random' or a [K x d] tensor expected" % (init,))
@@ -58,13 +42,12 @@ class KMeans:
             raise ValueError("KMeans: init of shape %s for n_clusters=%d" % (_shape(init), n_clusters))
         if not (n_init == 'auto' or (not isinstance(n_init, (bool, str)) and isinstance(n_init, (int, np.integer)) and n_init >= 1)):
             raise ValueError("KMeans: n_init=%r; 'auto' or an int >= 1 expected" % (n_init,))
-        for name, v in (("max_iter", max_iter), ("check_every", check_every)):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
-                raise ValueError("KMeans: %s=%r; an int >= 1 expected" % (name, v))
+        max_iter = _int_at_least("KMeans", "max_iter", max_iter, 1)
+        check_every = _int_at_least("KMeans", "check_every", check_every, 1)
         if not float(tol) >= 0.0:
             raise ValueError("KMeans: tol=%r; a number >= 0 expected" % (tol,))
-        self.n_clusters, self.init, self.n_init, self.max_iter, self.tol = int(n_clusters), init, n_init, int(max_iter), float(tol)
-        self.random_state, self.check_every, self.device = random_state, int(check_every), device
+        self.n_clusters, self.init, self.n_init, self.max_iter, self.tol = n_clusters, init, n_init, max_iter, float(tol)
+        self.random_state, self.check_every, self.device = random_state, check_every, device
         self.cluster_centers_ = self.labels_ = self.inertia_ = self.n_iter_ = self.n_relocations_ = None
         self.n_features_in_ = None
 
@@ -89,14 +72,6 @@ class KMeans:
             return int(self.n_init) if isinstance(self.init, str) else 1          # a given init has one run to make
         return 10 if isinstance(self.init, str) and self.init == 'random' else 1
 
-    def _generator(self):
-        g = torch.Generator()
-        if self.random_state is None:
-            g.seed()
-        else:
-            g.manual_seed(int(self.random_state))
-        return g
-
     def _seeds(self, x, g, ws):
         """the initial centres of one run, float64 [K x d] on the device (a fresh tensor: the run overwrites it)"""
         K = self.n_clusters
@@ -117,15 +92,8 @@ class KMeans:
         order = torch.empty(N, dtype=torch.int32, device=x.device)
         start = torch.empty(K + 1, dtype=torch.int32, device=x.device)
         state = ops.kmeans_state(x.device)
-        issued, record = 0, None
-        while issued < self.max_iter:
-            batch = min(self.check_every, self.max_iter - issued)
-            for _ in range(batch):
-                ops.kmeans_step(x, centres, labels, d2, order, start, tol_abs, state, ws)
-            issued += batch
-            record = state.cpu().numpy()                                          # the one read of the batch
-            if record[1] != 0.0:
-                break
+        record = _blind_batches(lambda: ops.kmeans_step(x, centres, labels, d2, order, start, tol_abs, state, ws), state,
+                                self.max_iter, self.check_every)
         return int(record[0]), int(record[5])
 
     def fit(self, X, y=None):
@@ -141,7 +109,7 @@ class KMeans:
                 cov = ops.pca_moments(x)[1]
                 tol_abs = self.tol * float((torch.diagonal(cov) * ((N - 1.0) / N)).mean().item())
             ws = ops.kmeans_workspace(N, d, self.n_clusters, x.device)
-            g = self._generator()
+            g = _generator(self.random_state)
             best = None
             for _ in range(self._runs()):
                 centres = self._seeds(x, g, ws)

@@ -1,6 +1,7 @@
 """The raw-launch layer of the fused training steps (evae/fused_vae.py, evae/fused_std.py) and of the dense autograd operators
 of evae/ops.py: the launcher over the dense entry points of the C ABI, the two job-table fillers, the beta pair (the one pointer
-conversion, vp, is evae/_lib.py's).  No autograd, caller-owned outputs.
+conversion, vp, is evae/_lib.py's).  No autograd, caller-owned outputs.  The same Launcher also carries the launchers of the
+latent-analysis entry points (tsne_*, nn_rank, pca_*, kmeans_*, cluster_*, silhouette_samples, gmm_*), one method per entry.
 
 The fused steps are stage functions over one per-step state object; the modular operators (GatedDenseFn, LinearFn, the heads'
 backward, the deferred weight gradients) are torch.autograd.Functions that build a Launcher where they run.  Every change to

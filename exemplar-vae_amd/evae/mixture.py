@@ -19,8 +19,9 @@ import numpy as np
 import torch
 
 from . import ops
+from ._fit import _blind_batches, _generator, _int_at_least, _rows, _shape
 from ._lib import EvaeError
-from .cluster import KMeans, _rows, _shape
+from .cluster import KMeans
 
 COVARIANCE_TYPES = ('full', 'diag', 'spherical')
 INIT_PARAMS = ('kmeans', 'random')
@@ -28,12 +29,6 @@ INIT_PARAMS = ('kmeans', 'random')
 ILL_DEFINED = ("Fitting the mixture model failed because some components have ill-defined empirical covariance (for instance "
                "caused by singleton or collapsed samples). Try to decrease the number of components, increase reg_covar, or "
                "scale the input data. The first such component is %d.")
-
-
-def _int_at_least(name, v, low):
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < low:
-        raise ValueError("GaussianMixture: %s=%r; an int >= %d expected" % (name, v, low))
-    return int(v)
 
 
 def _f64(a):
@@ -59,7 +54,7 @@ class GaussianMixture:
         what the initial M-step gave, as scikit-learn's.  n_init: runs; the one of highest lower bound wins (ties: the first).
         random_state seeds a CPU torch.Generator all draws come from; None draws a seed.  check_every: iterations issued between
         two reads of the device's record.  device: where a host array given to fit goes (default cuda)."""
-        n_components = _int_at_least("n_components", n_components, 1)
+        n_components = _int_at_least("GaussianMixture", "n_components", n_components, 1)
         if covariance_type == 'tied':
             raise ValueError("GaussianMixture: covariance_type='tied' is not carried over; 'full', 'diag' or 'spherical' expected")
         if covariance_type not in COVARIANCE_TYPES:
@@ -68,8 +63,9 @@ class GaussianMixture:
             raise ValueError("GaussianMixture: init_params=%r; 'kmeans' or 'random' expected" % (init_params,))
         if n_components > ops.gmm_max_components():
             raise ValueError("GaussianMixture: n_components=%d above the cap of %d" % (n_components, ops.gmm_max_components()))
-        max_iter, n_init = _int_at_least("max_iter", max_iter, 1), _int_at_least("n_init", n_init, 1)
-        check_every = _int_at_least("check_every", check_every, 1)
+        max_iter = _int_at_least("GaussianMixture", "max_iter", max_iter, 1)
+        n_init = _int_at_least("GaussianMixture", "n_init", n_init, 1)
+        check_every = _int_at_least("GaussianMixture", "check_every", check_every, 1)
         if not float(tol) >= 0.0:
             raise ValueError("GaussianMixture: tol=%r; a number >= 0 expected" % (tol,))
         if not float(reg_covar) >= 0.0:
@@ -122,14 +118,6 @@ class GaussianMixture:
             if _shape(self.precisions_init) != want:
                 raise ValueError("GaussianMixture: precisions_init of shape %s, %s expected" % (_shape(self.precisions_init), want))
 
-    def _generator(self):
-        g = torch.Generator()
-        if self.random_state is None:
-            g.seed()
-        else:
-            g.manual_seed(int(self.random_state))
-        return g
-
     def _raise_if_failed(self, record):
         if record[5] >= 0.0:
             raise ValueError(ILL_DEFINED % int(record[5]))
@@ -177,16 +165,8 @@ class GaussianMixture:
     def _em(self, x, params, ws, log_resp, logp):
         """params in place -> the record: batches of check_every blind steps, one read of the record per batch"""
         state = ops.gmm_state(x.device)
-        issued, record = 0, None
-        while issued < self.max_iter:
-            batch = min(self.check_every, self.max_iter - issued)
-            for _ in range(batch):
-                ops.gmm_step(x, params, self.n_components, self.covariance_type, log_resp, logp, self.reg_covar, self.tol, state, ws)
-            issued += batch
-            record = state.cpu().numpy()                                          # the one read of the batch
-            if record[1] != 0.0:
-                break
-        return record
+        return _blind_batches(lambda: ops.gmm_step(x, params, self.n_components, self.covariance_type, log_resp, logp,
+                                                   self.reg_covar, self.tol, state, ws), state, self.max_iter, self.check_every)
 
     def _fit(self, X):
         self._check(_shape(X))
@@ -197,7 +177,7 @@ class GaussianMixture:
             ws = ops.gmm_workspace(N, d, K, ctype, x.device)
             log_resp = torch.empty((N, K), dtype=torch.float64, device=x.device)
             logp = torch.empty(N, dtype=torch.float64, device=x.device)
-            g = self._generator()
+            g = _generator(self.random_state)
             best = None
             for run in range(self.n_init):
                 params = self._initial(x, g, run, ws)
@@ -269,10 +249,10 @@ class GaussianMixture:
         weights_ and standard normals, both from a CPU generator seeded with random_state"""
         if self._params is None:
             raise EvaeError("GaussianMixture: fit first")
-        n = _int_at_least("n_samples", n_samples, 1)
+        n = _int_at_least("GaussianMixture", "n_samples", n_samples, 1)
         if n > ops.gmm_max_points():
             raise ValueError("GaussianMixture: n_samples=%d above the cap of %d" % (n, ops.gmm_max_points()))
-        g = self._generator()
+        g = _generator(self.random_state)
         w = self.weights_.cpu().clamp_min(0.0)
         draws = torch.multinomial(w, n, replacement=True, generator=g)
         counts = torch.bincount(draws, minlength=self.n_components)

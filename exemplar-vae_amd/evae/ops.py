@@ -693,13 +693,12 @@ def tsne_knn(z, k, strip_rows=0):
     if z.dim() != 2:
         raise _lib.EvaeError("tsne_knn: a [N x zd] tensor expected, got %s" % (tuple(z.shape),))
     N, zd = z.shape
-    k, strip_rows = int(k), int(strip_rows)
+    k = int(k)
     if N > tsne_nn_max_points():
         raise _lib.EvaeError("tsne_knn: N=%d above the cap of %d points" % (N, tsne_nn_max_points()))
     if not 1 <= k <= min(N - 1, tsne_nn_max_neighbours()):
         raise _lib.EvaeError("tsne_knn: k=%d outside [1, min(N - 1 = %d, %d)]" % (k, N - 1, tsne_nn_max_neighbours()))
-    if strip_rows < 0:
-        raise _lib.EvaeError("tsne_knn: strip_rows=%d (0 = automatic)" % strip_rows)
+    strip_rows = _strip_rows(strip_rows, "tsne_knn")
     idx = torch.empty((N, k), dtype=torch.int32, device=z.device)
     d2 = torch.empty((N, k), device=z.device)
     ws = torch.empty(_lib.load().evae_tsne_knn_workspace_bytes(N, strip_rows), dtype=torch.uint8, device=z.device)
@@ -721,13 +720,12 @@ def nn_rank(z, nbr, strip_rows=0):
     N, zd = z.shape
     if nbr.dtype != torch.int32 or not nbr.is_contiguous() or nbr.dim() != 2 or nbr.shape[0] != N:
         raise _lib.EvaeError("nn_rank: nbr must be a contiguous int32 [%d x k] tensor" % N)
-    k, strip_rows = nbr.shape[1], int(strip_rows)
+    k = nbr.shape[1]
     if not 2 <= N <= tsne_nn_max_points():
         raise _lib.EvaeError("nn_rank: N=%d outside [2, %d]" % (N, tsne_nn_max_points()))
     if not 1 <= k <= min(N - 1, tsne_nn_max_neighbours()):
         raise _lib.EvaeError("nn_rank: k=%d outside [1, min(N - 1 = %d, %d)]" % (k, N - 1, tsne_nn_max_neighbours()))
-    if strip_rows < 0:
-        raise _lib.EvaeError("nn_rank: strip_rows=%d (0 = automatic)" % strip_rows)
+    strip_rows = _strip_rows(strip_rows, "nn_rank")
     rank = torch.empty((N, k), dtype=torch.int32, device=z.device)
     row_sums = torch.empty((N, 2), dtype=torch.int64, device=z.device)
     ws = torch.empty(_lib.load().evae_nn_rank_workspace_bytes(N, strip_rows), dtype=torch.uint8, device=z.device)
@@ -810,6 +808,37 @@ def tsne_nn_forces(row_ptr, col, val, Y, exaggeration=1.0, want_kl=False):
 
 
 # ------------------------------------------------------------------------------------------------
+# argument checks the latent-analysis entries share (the strip-wise ones above; PCA, k-means, the scores and the mixture below)
+# ------------------------------------------------------------------------------------------------
+def _strip_rows(strip_rows, who):
+    strip_rows = int(strip_rows)
+    if strip_rows < 0:
+        raise _lib.EvaeError("%s: strip_rows=%d (0 = automatic)" % (who, strip_rows))
+    return strip_rows
+
+
+def _dev_tensor(name, t, dtype, shape, who):
+    """what the kernels take, converted by nobody: a wrong dtype, shape or a strided tensor is refused"""
+    _need_cuda(t)
+    if t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+        raise _lib.EvaeError("%s: %s must be a contiguous %s %s tensor, got %s %s" % (who, name, dtype, list(shape), t.dtype,
+                                                                                     tuple(t.shape)))
+
+
+def _dev_rows(name, x, who, max_features=None, max_points=None):
+    """the rows of an entry, float32 [N x d] within the entry's caps (None: checked elsewhere) -> (N, d)"""
+    _need_cuda(x)
+    if x.dim() != 2 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise _lib.EvaeError("%s: %s must be a contiguous float32 [N x d] tensor, got %s %s" % (who, name, x.dtype, tuple(x.shape)))
+    N, d = x.shape
+    if max_features is not None and not 1 <= d <= max_features:
+        raise _lib.EvaeError("%s: %d features outside [1, %d]" % (who, d, max_features))
+    if max_points is not None and not 1 <= N <= max_points:
+        raise _lib.EvaeError("%s: N=%d outside [1, %d]" % (who, N, max_points))
+    return N, d
+
+
+# ------------------------------------------------------------------------------------------------
 # PCA in fp64 (csrc/evae_pca.hip, DESIGN 3.7c); the driver is evae/pca.py, TSNE(init='pca') its first user
 # ------------------------------------------------------------------------------------------------
 def pca_max_features():
@@ -831,29 +860,12 @@ def pca_max_sweeps():
     return int(_lib.load().evae_pca_max_sweeps())
 
 
-def _pca_f64(name, t, shape, who):
-    if t.dtype != torch.float64 or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
-        raise _lib.EvaeError("%s: %s must be a contiguous float64 %s tensor, got %s %s" % (who, name, list(shape), t.dtype,
-                                                                                          tuple(t.shape)))
-
-
-def _pca_rows(x, who):
-    _need_cuda(x)
-    x = _f32(x)
-    if x.dim() != 2:
-        raise _lib.EvaeError("%s: a [N x d] tensor expected, got %s" % (who, tuple(x.shape)))
-    if not 1 <= x.shape[1] <= pca_max_features():
-        raise _lib.EvaeError("%s: %d features outside [1, %d]" % (who, x.shape[1], pca_max_features()))
-    if not 1 <= x.shape[0] <= pca_max_points():
-        raise _lib.EvaeError("%s: N=%d outside [1, %d]" % (who, x.shape[0], pca_max_points()))
-    return x
-
-
 def pca_moments(x):
     """x [N x d] -> (mean [d], cov [d x d]), float64: the covariance (ddof 1) of the rows centred in fp64, two passes, symmetric
     bit for bit; equal inputs give bit-equal outputs."""
-    x = _pca_rows(x, "pca_moments")
-    N, d = x.shape
+    _need_cuda(x)
+    x = _f32(x)
+    N, d = _dev_rows("x", x, "pca_moments", pca_max_features(), pca_max_points())
     if N < 2:
         raise _lib.EvaeError("pca_moments: N=%d, at least 2 rows expected" % N)
     mean = torch.empty(d, dtype=torch.float64, device=x.device)
@@ -874,7 +886,7 @@ def pca_eigh(cov):
     d = cov.shape[0]
     if not 1 <= d <= pca_max_features():
         raise _lib.EvaeError("pca_eigh: d=%d outside [1, %d]" % (d, pca_max_features()))
-    _pca_f64("cov", cov, (d, d), "pca_eigh")
+    _dev_tensor("cov", cov, torch.float64, (d, d), "pca_eigh")
     evals = torch.empty(d, dtype=torch.float64, device=cov.device)
     evecs = torch.empty((d, d), dtype=torch.float64, device=cov.device)
     info = torch.empty(4, dtype=torch.float64, device=cov.device)
@@ -888,13 +900,13 @@ def pca_project(x, mean, comps, scale=1.0):
     """out [N x k] float32 = scale (x - mean) comps^T: x [N x d], mean [d] and comps [k x d] float64, 1 <= k <= d; accumulated
     in fp64, rounded once"""
     _need_cuda(x, mean, comps)
-    x = _pca_rows(x, "pca_project")
-    N, d = x.shape
+    x = _f32(x)
+    N, d = _dev_rows("x", x, "pca_project", pca_max_features(), pca_max_points())
     if comps.dim() != 2 or not 1 <= comps.shape[0] <= d:
         raise _lib.EvaeError("pca_project: comps must be [k x %d] with 1 <= k <= %d, got %s" % (d, d, tuple(comps.shape)))
     k = comps.shape[0]
-    _pca_f64("mean", mean, (d,), "pca_project")
-    _pca_f64("comps", comps, (k, d), "pca_project")
+    _dev_tensor("mean", mean, torch.float64, (d,), "pca_project")
+    _dev_tensor("comps", comps, torch.float64, (k, d), "pca_project")
     out = torch.empty((N, k), device=x.device)
     launch.Launcher(x.device).pca_project(x, N, d, mean, comps, k, scale, out)
     return out
@@ -903,14 +915,14 @@ def pca_project(x, mean, comps, scale=1.0):
 def pca_reconstruct(y, mean, comps):
     """out [N x d] float32 = mean + y comps: y [N x k], the reverse map of pca_project at scale 1"""
     _need_cuda(y, mean, comps)
-    y = _pca_rows(y, "pca_reconstruct")
-    N, k = y.shape
+    y = _f32(y)
+    N, k = _dev_rows("y", y, "pca_reconstruct", pca_max_features(), pca_max_points())
     if comps.dim() != 2 or comps.shape[0] != k or not k <= comps.shape[1] <= pca_max_features():
         raise _lib.EvaeError("pca_reconstruct: comps must be [%d x d] with %d <= d <= %d, got %s"
                              % (k, k, pca_max_features(), tuple(comps.shape)))
     d = comps.shape[1]
-    _pca_f64("mean", mean, (d,), "pca_reconstruct")
-    _pca_f64("comps", comps, (k, d), "pca_reconstruct")
+    _dev_tensor("mean", mean, torch.float64, (d,), "pca_reconstruct")
+    _dev_tensor("comps", comps, torch.float64, (k, d), "pca_reconstruct")
     out = torch.empty((N, d), device=y.device)
     launch.Launcher(y.device).pca_reconstruct(y, N, k, mean, comps, d, out)
     return out
@@ -945,29 +957,20 @@ def kmeans_centre_tile():
     return int(_lib.load().evae_kmeans_centre_tile())
 
 
-def _km_tensor(name, t, dtype, shape, who):
-    _need_cuda(t)
-    if t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
-        raise _lib.EvaeError("%s: %s must be a contiguous %s %s tensor, got %s %s" % (who, name, dtype, list(shape), t.dtype,
-                                                                                     tuple(t.shape)))
-
-
-def _km_rows(x, who, max_points=None):
-    _need_cuda(x)
-    if x.dim() != 2 or x.dtype != torch.float32 or not x.is_contiguous():
-        raise _lib.EvaeError("%s: x must be a contiguous float32 [N x d] tensor, got %s %s" % (who, x.dtype, tuple(x.shape)))
-    N, d = x.shape
-    if not 1 <= d <= kmeans_max_features():
-        raise _lib.EvaeError("%s: %d features outside [1, %d]" % (who, d, kmeans_max_features()))
-    if not 1 <= N <= (max_points or kmeans_max_points()):
-        raise _lib.EvaeError("%s: N=%d outside [1, %d]" % (who, N, max_points or kmeans_max_points()))
-    return N, d
-
-
 def _km_clusters(K, who, N=None):
     K = int(K)
     if not 1 <= K <= kmeans_max_clusters() or (N is not None and K > N):
         raise _lib.EvaeError("%s: K=%d outside [1, min(N, %d)]" % (who, K, kmeans_max_clusters()))
+    return K
+
+
+def _km_centres(centres, d, who, N=None):
+    """centres float64 [K x d] (K <= N where N is given) -> K"""
+    _need_cuda(centres)
+    if centres.dim() != 2:
+        raise _lib.EvaeError("%s: centres must be [K x %d], got %s" % (who, d, tuple(centres.shape)))
+    K = _km_clusters(centres.shape[0], who, N)
+    _dev_tensor("centres", centres, torch.float64, (K, d), who)
     return K
 
 
@@ -979,12 +982,8 @@ def kmeans_workspace(N, d, K, device):
 def kmeans_assign(x, centres):
     """x [N x d] float32, centres [K x d] float64 -> (labels int32 [N], d2 float64 [N]): the nearest centre by
     sum_k (x_ik - c_jk)^2 in fp64, k ascending, ties to the lowest index; d2 is the winning sum"""
-    N, d = _km_rows(x, "kmeans_assign")
-    _need_cuda(centres)
-    if centres.dim() != 2:
-        raise _lib.EvaeError("kmeans_assign: centres must be [K x %d], got %s" % (d, tuple(centres.shape)))
-    K = _km_clusters(centres.shape[0], "kmeans_assign")
-    _km_tensor("centres", centres, torch.float64, (K, d), "kmeans_assign")
+    N, d = _dev_rows("x", x, "kmeans_assign", kmeans_max_features(), kmeans_max_points())
+    K = _km_centres(centres, d, "kmeans_assign")
     labels = torch.empty(N, dtype=torch.int32, device=x.device)
     d2 = torch.empty(N, dtype=torch.float64, device=x.device)
     launch.Launcher(x.device).kmeans_assign(x, N, d, centres, K, labels, d2)
@@ -994,12 +993,8 @@ def kmeans_assign(x, centres):
 def kmeans_transform(x, centres):
     """x [N x d] float32, centres [K x d] float64 -> float32 [N x K]: the distances (not squared) to every centre, the sums of
     kmeans_assign, one square root and one rounding each"""
-    N, d = _km_rows(x, "kmeans_transform")
-    _need_cuda(centres)
-    if centres.dim() != 2:
-        raise _lib.EvaeError("kmeans_transform: centres must be [K x %d], got %s" % (d, tuple(centres.shape)))
-    K = _km_clusters(centres.shape[0], "kmeans_transform")
-    _km_tensor("centres", centres, torch.float64, (K, d), "kmeans_transform")
+    N, d = _dev_rows("x", x, "kmeans_transform", kmeans_max_features(), kmeans_max_points())
+    K = _km_centres(centres, d, "kmeans_transform")
     out = torch.empty((N, K), dtype=torch.float32, device=x.device)
     launch.Launcher(x.device).kmeans_transform(x, N, d, centres, K, out)
     return out
@@ -1009,9 +1004,9 @@ def kmeans_update(x, labels, K, ws=None):
     """x [N x d], labels int32 [N] in [0, K) -> (order int32 [N], start int32 [K + 1], sums float64 [K x d]): the stable counting
     sort of the rows by label (cluster c owns order[start[c] : start[c + 1]], in index order) and the fp64 column sums of every
     cluster in a fixed order.  A label outside [0, K) is left out of all three (labels are trusted, the kernels only guard)."""
-    N, d = _km_rows(x, "kmeans_update")
+    N, d = _dev_rows("x", x, "kmeans_update", kmeans_max_features(), kmeans_max_points())
     K = _km_clusters(K, "kmeans_update")
-    _km_tensor("labels", labels, torch.int32, (N,), "kmeans_update")
+    _dev_tensor("labels", labels, torch.int32, (N,), "kmeans_update")
     order = torch.empty(N, dtype=torch.int32, device=x.device)
     start = torch.empty(K + 1, dtype=torch.int32, device=x.device)
     sums = torch.empty((K, d), dtype=torch.float64, device=x.device)
@@ -1029,17 +1024,13 @@ def kmeans_step(x, centres, labels, d2, order, start, tol_abs, state, ws):
     """One Lloyd iteration in place (assign + update + finish on the current stream): centres [K x d] float64 are replaced by
     the means of their clusters, labels / d2 / order / start belong to the centres that came in, state (kmeans_state) is advanced.
     Once state[1] (done) is set, further calls change nothing: a caller may issue several and read the record once."""
-    N, d = _km_rows(x, "kmeans_step")
-    _need_cuda(centres)
-    if centres.dim() != 2:
-        raise _lib.EvaeError("kmeans_step: centres must be [K x %d], got %s" % (d, tuple(centres.shape)))
-    K = _km_clusters(centres.shape[0], "kmeans_step", N)
-    _km_tensor("centres", centres, torch.float64, (K, d), "kmeans_step")
-    _km_tensor("labels", labels, torch.int32, (N,), "kmeans_step")
-    _km_tensor("d2", d2, torch.float64, (N,), "kmeans_step")
-    _km_tensor("order", order, torch.int32, (N,), "kmeans_step")
-    _km_tensor("start", start, torch.int32, (K + 1,), "kmeans_step")
-    _km_tensor("state", state, torch.float64, (KMEANS_STATE,), "kmeans_step")
+    N, d = _dev_rows("x", x, "kmeans_step", kmeans_max_features(), kmeans_max_points())
+    K = _km_centres(centres, d, "kmeans_step", N)
+    _dev_tensor("labels", labels, torch.int32, (N,), "kmeans_step")
+    _dev_tensor("d2", d2, torch.float64, (N,), "kmeans_step")
+    _dev_tensor("order", order, torch.int32, (N,), "kmeans_step")
+    _dev_tensor("start", start, torch.int32, (K + 1,), "kmeans_step")
+    _dev_tensor("state", state, torch.float64, (KMEANS_STATE,), "kmeans_step")
     _need_cuda(ws)
     if not float(tol_abs) >= 0.0:
         raise _lib.EvaeError("kmeans_step: tol_abs=%r" % (tol_abs,))
@@ -1052,9 +1043,9 @@ def kmeans_seed(x, K, u, ws=None):
     min-distances (chunks in order, rows in order) exceeds u_t times their total; when the total is 0 (fewer distinct rows than
     centres) it is the lowest index not chosen yet.  scikit-learn's greedy local trials are not carried over: one candidate per
     centre."""
-    N, d = _km_rows(x, "kmeans_seed")
+    N, d = _dev_rows("x", x, "kmeans_seed", kmeans_max_features(), kmeans_max_points())
     K = _km_clusters(K, "kmeans_seed", N)
-    _km_tensor("u", u, torch.float64, (K,), "kmeans_seed")
+    _dev_tensor("u", u, torch.float64, (K,), "kmeans_seed")
     idx = torch.empty(K, dtype=torch.int32, device=x.device)
     centres = torch.empty((K, d), dtype=torch.float64, device=x.device)
     ws = kmeans_workspace(N, d, K, x.device) if ws is None else ws
@@ -1068,7 +1059,7 @@ def kmeans_inertia(d2):
     if d2.dim() != 1 or not 1 <= d2.shape[0] <= kmeans_max_points():
         raise _lib.EvaeError("kmeans_inertia: d2 must be [N], N in [1, %d], got %s" % (kmeans_max_points(), tuple(d2.shape)))
     N = d2.shape[0]
-    _km_tensor("d2", d2, torch.float64, (N,), "kmeans_inertia")
+    _dev_tensor("d2", d2, torch.float64, (N,), "kmeans_inertia")
     out = torch.empty(1, dtype=torch.float64, device=d2.device)
     ws = torch.empty(8 * ((N + kmeans_chunk_rows() - 1) // kmeans_chunk_rows()), dtype=torch.uint8, device=d2.device)
     launch.Launcher(d2.device).kmeans_inertia(d2, N, out, ws)
@@ -1081,8 +1072,8 @@ def cluster_contingency(a, Ka, b, Kb):
     if a.dim() != 1 or not 1 <= a.shape[0] <= kmeans_max_points():
         raise _lib.EvaeError("cluster_contingency: a must be [N], N in [1, %d], got %s" % (kmeans_max_points(), tuple(a.shape)))
     N = a.shape[0]
-    _km_tensor("a", a, torch.int32, (N,), "cluster_contingency")
-    _km_tensor("b", b, torch.int32, (N,), "cluster_contingency")
+    _dev_tensor("a", a, torch.int32, (N,), "cluster_contingency")
+    _dev_tensor("b", b, torch.int32, (N,), "cluster_contingency")
     Ka, Kb = _km_clusters(Ka, "cluster_contingency"), _km_clusters(Kb, "cluster_contingency")
     table = torch.empty((Ka, Kb), dtype=torch.int64, device=a.device)
     launch.Launcher(a.device).cluster_contingency(a, Ka, b, Kb, N, table)
@@ -1099,7 +1090,7 @@ def cluster_scores(table):
     if table.dim() != 2:
         raise _lib.EvaeError("cluster_scores: a [Ka x Kb] table expected, got %s" % (tuple(table.shape),))
     Ka, Kb = _km_clusters(table.shape[0], "cluster_scores"), _km_clusters(table.shape[1], "cluster_scores")
-    _km_tensor("table", table, torch.int64, (Ka, Kb), "cluster_scores")
+    _dev_tensor("table", table, torch.int64, (Ka, Kb), "cluster_scores")
     out = torch.empty(8, dtype=torch.float64, device=table.device)
     launch.Launcher(table.device).cluster_scores(table, Ka, Kb, out)
     return out
@@ -1110,17 +1101,16 @@ def silhouette_samples(x, order, start, strip_rows=0):
     rest of i's cluster, b_i the smallest mean distance to another non-empty cluster; 0 for a singleton and for max(a, b) = 0.
     Distances are sqrt of pairwise_distance's squared ones, strip by strip (strip_rows query rows, 0: what fits 256 MiB); the
     result does not depend on strip_rows."""
-    N, d = _km_rows(x, "silhouette_samples", tsne_nn_max_points())
+    N, d = _dev_rows("x", x, "silhouette_samples", kmeans_max_features(), tsne_nn_max_points())
     if N < 2:
         raise _lib.EvaeError("silhouette_samples: N=%d, at least 2 rows expected" % N)
     _need_cuda(start)
     if start.dim() != 1 or not 2 <= start.shape[0] <= N + 1:
         raise _lib.EvaeError("silhouette_samples: start must be [K + 1] with 1 <= K <= N=%d, got %s" % (N, tuple(start.shape)))
-    K, strip_rows = start.shape[0] - 1, int(strip_rows)
-    _km_tensor("order", order, torch.int32, (N,), "silhouette_samples")
-    _km_tensor("start", start, torch.int32, (K + 1,), "silhouette_samples")
-    if strip_rows < 0:
-        raise _lib.EvaeError("silhouette_samples: strip_rows=%d (0 = automatic)" % strip_rows)
+    K = start.shape[0] - 1
+    _dev_tensor("order", order, torch.int32, (N,), "silhouette_samples")
+    _dev_tensor("start", start, torch.int32, (K + 1,), "silhouette_samples")
+    strip_rows = _strip_rows(strip_rows, "silhouette_samples")
     out = torch.zeros(N, dtype=torch.float64, device=x.device)
     ws = torch.empty(_lib.load().evae_silhouette_workspace_bytes(N, d, strip_rows), dtype=torch.uint8, device=x.device)
     launch.Launcher(x.device).silhouette_samples(x, N, d, order, start, K, out, ws, strip_rows)
@@ -1187,13 +1177,6 @@ def gmm_check_sizes(N, d, K, covariance_type, who):
                              % (who, resp, ws, N, d, K, gmm_max_bytes()))
 
 
-def _gmm_rows(x, who):
-    _need_cuda(x)
-    if x.dim() != 2 or x.dtype != torch.float32 or not x.is_contiguous():
-        raise _lib.EvaeError("%s: x must be a contiguous float32 [N x d] tensor, got %s %s" % (who, x.dtype, tuple(x.shape)))
-    return x.shape
-
-
 def gmm_params(d, K, covariance_type, device):
     """an uninitialised parameter buffer (float64) for these sizes"""
     gmm_check_sizes(None, d, K, covariance_type, "gmm_params")
@@ -1212,11 +1195,16 @@ def gmm_views(params, d, K, covariance_type):
                 precisions_cholesky=params[o + 2 * K * d + K * cs:o + 2 * K * d + 2 * K * cs].view(shape))
 
 
+def _gmm_params(params, d, K, covariance_type, who):
+    """`params` must be the one buffer gmm_params lays out for these (already checked) sizes"""
+    n = _lib.load().evae_gmm_params_doubles(int(d), int(K), GMM_TYPES[covariance_type])
+    _dev_tensor("params", params, torch.float64, (n,), who)
+
+
 def _gmm_args(x, params, K, covariance_type, who):
-    N, d = _gmm_rows(x, who)
+    N, d = _dev_rows("x", x, who)                            # the caps depend on the covariance type: gmm_check_sizes
     gmm_check_sizes(N, d, int(K), covariance_type, who)
-    n = _lib.load().evae_gmm_params_doubles(d, int(K), GMM_TYPES[covariance_type])
-    _km_tensor("params", params, torch.float64, (n,), who)
+    _gmm_params(params, d, K, covariance_type, who)
     return N, d, int(K), GMM_TYPES[covariance_type]
 
 
@@ -1235,8 +1223,8 @@ def gmm_estep(x, params, K, covariance_type, ws=None, log_resp=None, logp=None):
     N, d, K, t = _gmm_args(x, params, K, covariance_type, "gmm_estep")
     log_resp = torch.empty((N, K), dtype=torch.float64, device=x.device) if log_resp is None else log_resp
     logp = torch.empty(N, dtype=torch.float64, device=x.device) if logp is None else logp
-    _km_tensor("log_resp", log_resp, torch.float64, (N, K), "gmm_estep")
-    _km_tensor("logp", logp, torch.float64, (N,), "gmm_estep")
+    _dev_tensor("log_resp", log_resp, torch.float64, (N, K), "gmm_estep")
+    _dev_tensor("logp", logp, torch.float64, (N,), "gmm_estep")
     mean = torch.empty(1, dtype=torch.float64, device=x.device)
     ws = gmm_workspace(N, d, K, covariance_type, x.device) if ws is None else ws
     _need_cuda(ws)
@@ -1251,10 +1239,10 @@ def gmm_mstep(x, params, K, covariance_type, reg_covar, state, log_resp=None, la
     if (log_resp is None) == (labels is None):
         raise _lib.EvaeError("gmm_mstep: exactly one of log_resp and labels expected")
     if log_resp is not None:
-        _km_tensor("log_resp", log_resp, torch.float64, (N, K), "gmm_mstep")
+        _dev_tensor("log_resp", log_resp, torch.float64, (N, K), "gmm_mstep")
     else:
-        _km_tensor("labels", labels, torch.int32, (N,), "gmm_mstep")
-    _km_tensor("state", state, torch.float64, (GMM_STATE,), "gmm_mstep")
+        _dev_tensor("labels", labels, torch.int32, (N,), "gmm_mstep")
+    _dev_tensor("state", state, torch.float64, (GMM_STATE,), "gmm_mstep")
     if not float(reg_covar) >= 0.0:
         raise _lib.EvaeError("gmm_mstep: reg_covar=%r" % (reg_covar,))
     ws = gmm_workspace(N, d, K, covariance_type, x.device) if ws is None else ws
@@ -1266,9 +1254,9 @@ def gmm_step(x, params, K, covariance_type, log_resp, logp, reg_covar, tol, stat
     """One EM iteration in place (E-step, M-step, record: six launches on the current stream).  Once state[1] (done) is set,
     further calls change nothing: a caller may issue several and read the record once."""
     N, d, K, t = _gmm_args(x, params, K, covariance_type, "gmm_step")
-    _km_tensor("log_resp", log_resp, torch.float64, (N, K), "gmm_step")
-    _km_tensor("logp", logp, torch.float64, (N,), "gmm_step")
-    _km_tensor("state", state, torch.float64, (GMM_STATE,), "gmm_step")
+    _dev_tensor("log_resp", log_resp, torch.float64, (N, K), "gmm_step")
+    _dev_tensor("logp", logp, torch.float64, (N,), "gmm_step")
+    _dev_tensor("state", state, torch.float64, (GMM_STATE,), "gmm_step")
     _need_cuda(ws)
     if not float(reg_covar) >= 0.0 or not float(tol) >= 0.0:
         raise _lib.EvaeError("gmm_step: reg_covar=%r, tol=%r" % (reg_covar, tol))
@@ -1278,8 +1266,7 @@ def gmm_step(x, params, K, covariance_type, log_resp, logp, reg_covar, tol, stat
 def gmm_prepare(params, d, K, covariance_type):
     """b = mu P and log_det = sum log diag P from the means and factors already in params"""
     gmm_check_sizes(None, d, int(K), covariance_type, "gmm_prepare")
-    n = _lib.load().evae_gmm_params_doubles(int(d), int(K), GMM_TYPES[covariance_type])
-    _km_tensor("params", params, torch.float64, (n,), "gmm_prepare")
+    _gmm_params(params, d, K, covariance_type, "gmm_prepare")
     launch.Launcher(params.device).gmm_prepare(params, int(d), int(K), GMM_TYPES[covariance_type])
 
 
@@ -1289,7 +1276,7 @@ def gmm_argmax(log_resp):
     if log_resp.dim() != 2 or not 1 <= log_resp.shape[0] <= gmm_max_points() or not 1 <= log_resp.shape[1] <= gmm_max_components():
         raise _lib.EvaeError("gmm_argmax: log_resp must be [N x K] within the caps, got %s" % (tuple(log_resp.shape),))
     N, K = log_resp.shape
-    _km_tensor("log_resp", log_resp, torch.float64, (N, K), "gmm_argmax")
+    _dev_tensor("log_resp", log_resp, torch.float64, (N, K), "gmm_argmax")
     labels = torch.empty(N, dtype=torch.int32, device=log_resp.device)
     launch.Launcher(log_resp.device).gmm_argmax(log_resp, N, K, labels)
     return labels
@@ -1298,14 +1285,13 @@ def gmm_argmax(log_resp):
 def gmm_sample(params, d, K, covariance_type, comp, eps):
     """comp int32 [n] in [0, K), eps float64 [n x d] standard normals -> float32 [n x d]: mu_c + (P_c^T)^-1 eps"""
     gmm_check_sizes(None, d, int(K), covariance_type, "gmm_sample")
-    n_par = _lib.load().evae_gmm_params_doubles(int(d), int(K), GMM_TYPES[covariance_type])
-    _km_tensor("params", params, torch.float64, (n_par,), "gmm_sample")
+    _gmm_params(params, d, K, covariance_type, "gmm_sample")
     _need_cuda(comp, eps)
     if comp.dim() != 1 or not 1 <= comp.shape[0] <= gmm_max_points():
         raise _lib.EvaeError("gmm_sample: comp must be [n], n in [1, %d], got %s" % (gmm_max_points(), tuple(comp.shape)))
     n = comp.shape[0]
-    _km_tensor("comp", comp, torch.int32, (n,), "gmm_sample")
-    _km_tensor("eps", eps, torch.float64, (n, d), "gmm_sample")
+    _dev_tensor("comp", comp, torch.int32, (n,), "gmm_sample")
+    _dev_tensor("eps", eps, torch.float64, (n, d), "gmm_sample")
     z = torch.empty((n, d), dtype=torch.float32, device=params.device)
     launch.Launcher(params.device).gmm_sample(params, int(d), int(K), GMM_TYPES[covariance_type], comp, eps, n, z)
     return z
