@@ -1,7 +1,8 @@
 // The one copy of the blocks the latent-analysis kernels share: evae_tsne_nn.hip, evae_nn_rank.hip, evae_pca.hip,
-// evae_kmeans.hip, evae_gmm.hip.  They all rest on one contract -- fp64 arithmetic on fp32 rows, no
-// floating-point atomics, every sum in a fixed order, equal inputs giving bit-equal outputs -- and this header carries it:
-// nothing here changes the order of a sum, and a helper that would need to know which caller it serves does not belong here.
+// evae_kmeans.hip, evae_gmm.hip, evae_ball_count.hip.  They all rest on one contract -- fp64 arithmetic on
+// fp32 rows, no floating-point atomics, every sum in a fixed order, equal inputs giving bit-equal outputs -- and this header
+// carries it: nothing here changes the order of a sum, and a helper that would need to know which caller it serves does not
+// belong here.
 // tests/test_gpu_latent_bits.py holds the callers to the bits they gave before the blocks were shared.
 #pragma once
 #include "evae_common.h"
@@ -102,6 +103,28 @@ static inline int for_each_strip(const float* x, int N, int d, int R, float* str
   for (int r0 = 0; r0 < N; r0 += R) {
     const int rows = N - r0 < R ? N - r0 : R;
     int rc = evae_pairwise_distance(x + (size_t)r0 * d, rows, x, N, d, strip, stream);
+    if (rc) return rc;
+    if ((rc = reader(r0, rows))) return rc;
+  }
+  return EVAE_OK;
+}
+
+// The cross-set siblings: B query rows from one array, N columns from another.  The same byte rule on the column count; the
+// strip is never longer than the queries.
+static inline int cross_strip_rows_of(int B, int N, int strip_rows) {
+  size_t r = strip_rows > 0 ? (size_t)strip_rows : kStripBytes / ((size_t)N * sizeof(float));
+  if (strip_rows <= 0 && r >= 64) r &= ~(size_t)63;
+  if (r < 1) r = 1;
+  return r > (size_t)B ? B : (int)r;
+}
+
+// The squared distances of q's rows r0 .. r0 + rows to all N rows of c, R rows at a time into `strip`
+template <typename Reader>
+static inline int for_each_cross_strip(const float* q, int B, const float* c, int N, int d, int R, float* strip,
+                                       evae_stream_t stream, Reader reader) {
+  for (int r0 = 0; r0 < B; r0 += R) {
+    const int rows = B - r0 < R ? B - r0 : R;
+    int rc = evae_pairwise_distance(q + (size_t)r0 * d, rows, c, N, d, strip, stream);
     if (rc) return rc;
     if ((rc = reader(r0, rows))) return rc;
   }

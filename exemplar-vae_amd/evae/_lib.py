@@ -263,6 +263,9 @@ SIGNATURES = {
     "evae_tsne_nn_forces": (_i, [_p, _p, _p, _p, _i, _d, _i, _p, _p, _z, _p]),
     "evae_nn_rank_workspace_bytes": (_z, [_i, _i]),
     "evae_nn_rank": (_i, [_p, _i, _i, _p, _i, _i, _p, _p, _p, _z, _p]),
+    "evae_ball_count_max_points": (_i, []),
+    "evae_ball_count_workspace_bytes": (_z, [_i, _i, _i]),
+    "evae_ball_count": (_i, [_p, _i, _p, _i, _i, _p, _p, _i, _p, _p, _p, _p, _p, _z, _p]),
     "evae_pca_max_features": (_i, []),
     "evae_pca_max_points": (_i, []),
     "evae_pca_chunk_rows": (_i, []),

@@ -189,6 +189,11 @@ class Launcher:
         _lib.check(self.lib.evae_nn_rank(vp(z), N, zd, vp(nbr), int(k), int(strip_rows), vp(rank), vp(row_sums), vp(ws), ws.numel(),
                                          self.st), "nn_rank")
 
+    def ball_count(self, q, B, c, N, d, col_radius, row_radius, strip_rows, col_hits, row_hits, nn_idx, nn_d2, ws):
+        """csrc/evae_ball_count.hip: None switches a radius and its count, or a half of the nearest pair, off"""
+        _lib.check(self.lib.evae_ball_count(vp(q), B, vp(c), N, d, vp(col_radius), vp(row_radius), int(strip_rows), vp(col_hits),
+                                            vp(row_hits), vp(nn_idx), vp(nn_d2), vp(ws), ws.numel(), self.st), "ball_count")
+
     def tsne_nn_conditionals(self, d2, N, k, perplexity, steps, beta, cond):
         _lib.check(self.lib.evae_tsne_nn_conditionals(vp(d2), N, int(k), float(perplexity), int(steps), vp(beta), vp(cond), self.st),
                    "tsne_nn_conditionals")

@@ -733,6 +733,52 @@ def nn_rank(z, nbr, strip_rows=0):
     return rank, row_sums
 
 
+def ball_count_max_points():
+    """largest B and N of ball_count: the cap of the neighbour search its radii come from"""
+    return int(_lib.load().evae_ball_count_max_points())
+
+
+BallCount = collections.namedtuple("BallCount", "col_hits row_hits nn_idx nn_d2")
+
+
+def ball_count(q, c, col_radius=None, row_radius=None, want_nearest=True, strip_rows=0):
+    """q [B x d], c [N x d] -> BallCount(col_hits, row_hits, nn_idx, nn_d2) (csrc/evae_ball_count.hip):
+    col_hits[i] = #{ j : D(q_i, c_j) < col_radius[j] }, row_hits[i] = #{ j : D(q_i, c_j) < row_radius[i] } (int32 [B]) and
+    (nn_d2[i], nn_idx[i]) = the minimum of (D(q_i, c_j), j): the nearest column, the lower index on a tie.  D is
+    pairwise_distance's fp32 value and every comparison strict, so radii from tsne_knn compare with the distances they were taken
+    from.  A radius of None switches its count off, want_nearest=False the nearest pair; what is off is None.  Exact integers;
+    the result does not depend on strip_rows (query rows per strip of distances, 0: what fits 256 MiB)."""
+    _need_cuda(q, c, col_radius, row_radius)
+    q, c = _f32(q), _f32(c)
+    if q.dim() != 2 or c.dim() != 2:
+        raise _lib.EvaeError("ball_count: [B x d] and [N x d] tensors expected, got %s and %s" % (tuple(q.shape), tuple(c.shape)))
+    (B, d), (N, dc) = q.shape, c.shape
+    if d != dc or d < 1:
+        raise _lib.EvaeError("ball_count: q has %d features, c has %d (equal and >= 1 expected)" % (d, dc))
+    cap = ball_count_max_points()
+    if not (1 <= B <= cap and 1 <= N <= cap):
+        raise _lib.EvaeError("ball_count: B=%d, N=%d outside [1, %d]" % (B, N, cap))
+    if col_radius is not None:
+        _dev_tensor("col_radius", col_radius, torch.float32, (N,), "ball_count")
+    if row_radius is not None:
+        _dev_tensor("row_radius", row_radius, torch.float32, (B,), "ball_count")
+    if col_radius is None and row_radius is None and not want_nearest:
+        raise _lib.EvaeError("ball_count: no output asked for (no radius and want_nearest=False)")
+    strip_rows = _strip_rows(strip_rows, "ball_count")
+    col_hits = torch.empty(B, dtype=torch.int32, device=q.device) if col_radius is not None else None
+    row_hits = torch.empty(B, dtype=torch.int32, device=q.device) if row_radius is not None else None
+    nn_idx = torch.empty(B, dtype=torch.int32, device=q.device) if want_nearest else None
+    nn_d2 = torch.empty(B, device=q.device) if want_nearest else None
+    ws = torch.empty(_lib.load().evae_ball_count_workspace_bytes(B, N, strip_rows), dtype=torch.uint8, device=q.device)
+    launch.Launcher(q.device).ball_count(q, B, c, N, d, col_radius, row_radius, strip_rows, col_hits, row_hits, nn_idx, nn_d2, ws)
+    return BallCount(col_hits, row_hits, nn_idx, nn_d2)
+
+
+def kth_neighbour_radius(x, k, strip_rows=0):
+    """x [N x d] -> float32 [N]: the squared distance from every row to its k-th nearest OTHER row (tsne_knn's column k - 1)"""
+    return tsne_knn(x, k, strip_rows)[1][:, int(k) - 1].contiguous()
+
+
 def tsne_nn_conditionals(d2, perplexity, steps=TSNE_SEARCH_STEPS):
     """d2 [N x k] from tsne_knn -> (beta [N], cond [N x k]): the precision search of tsne_affinities over each row's k values
     and the row's conditional p(j|i) on them (rows sum to 1)."""

@@ -1011,6 +1011,37 @@ int evae_nn_rank(const float* z /* [N x zdim] */, int N, int zdim, const int* nb
                  evae_stream_t stream);
 
 /* ----------------------------------------------------------------------------------------------
+ * Ball counts and nearest columns between two sets of rows: what precision, recall, density, coverage and authenticity of
+ * generated samples are sums of (evae/sample_quality.py).  csrc/evae_ball_count.hip; DESIGN 3.7f.  No [B x N] buffer exists
+ * at any point.
+ *
+ * ball_count: q [B x d], c [N x d] ->
+ *     col_hits[i] = #{ j : D(q_i, c_j) < col_radius[j] }      (col_radius [N])
+ *     row_hits[i] = #{ j : D(q_i, c_j) < row_radius[i] }      (row_radius [B])
+ *     (nn_d2[i], nn_idx[i]) = the minimum over j of (D(q_i, c_j), j), lexicographic: the nearest column, the lower index on a tie.
+ *   D as evae_pairwise_distance gives it (direct differences accumulated in fp64, rounded once to fp32); every comparison is
+ *   strict and on those fp32 values, so a radius from evae_tsne_knn's d2 is compared with the distances it was taken from.
+ *   A NULL radius switches its count off: col_hits must be NULL exactly when col_radius is, row_hits exactly when row_radius
+ *   is.  nn_idx and nn_d2 may each be NULL; at least one output must be asked for.
+ *   Finite inputs are the caller's contract, as in the neighbour search.  A NaN distance or radius fails every comparison and
+ *   is in no ball; a NaN's bit pattern orders above +inf's, so a NaN distance is the minimum only of a row whose distances are
+ *   all NaN (nn_d2 is then a NaN, nn_idx the column of the lowest bit pattern).
+ *   1 <= B, N <= evae_ball_count_max_points() = evae_tsne_nn_max_points(), d >= 1.  The queries go in strips of strip_rows rows
+ *   (0: as many as fit 256 MiB of distances, the rule of the neighbour search on the column count N; never more than B); ws
+ *   holds one strip, evae_ball_count_workspace_bytes(B, N, strip_rows) bytes.  Two launches per strip: the distances, then one
+ *   workgroup per row that streams the row's N distances once in 16-byte loads (peeled to the row's alignment; the radii are
+ *   read as scalars) and produces every requested output of the row.  Integer add and an integer minimum of
+ *   (distance bits << 32) | j only, no atomics: the result is exact, the same on every run and does not depend on strip_rows.
+ */
+int evae_ball_count_max_points(void);
+size_t evae_ball_count_workspace_bytes(int B, int N, int strip_rows);
+int evae_ball_count(const float* q /* [B x d] */, int B, const float* c /* [N x d] */, int N, int d,
+                    const float* col_radius /* [N] or NULL */, const float* row_radius /* [B] or NULL */,
+                    int strip_rows, int* col_hits /* [B] or NULL */, int* row_hits /* [B] or NULL */,
+                    int* nn_idx /* [B] or NULL */, float* nn_d2 /* [B] or NULL */,
+                    void* ws, size_t ws_bytes, evae_stream_t stream);
+
+/* ----------------------------------------------------------------------------------------------
  * PCA of the latent space in fp64 (evae/pca.py; TSNE(init='pca')).  csrc/evae_pca.hip; DESIGN 3.7c.  Inputs are contiguous
  * fp32 [N x d]; every accumulation is fp64, there are no floating-point atomics and every sum has a fixed order, so equal
  * inputs give bit-equal outputs.  1 <= d <= evae_pca_max_features() = 256, 2 <= N <= evae_pca_max_points() = 2^20.
