@@ -306,6 +306,11 @@ SIGNATURES = {
     "evae_gmm_prepare": (_i, [_p, _i, _i, _i, _p]),
     "evae_gmm_argmax": (_i, [_p, _i, _i, _p, _p]),
     "evae_gmm_sample": (_i, [_p, _i, _i, _i, _p, _p, _i, _p, _p]),
+    "evae_agg_lse_max_features": (_i, []),
+    "evae_agg_lse_max_points": (_i, []),
+    "evae_agg_lse_tile": (_i, []),
+    "evae_agg_lse_workspace_bytes": (_z, [_i, _i, _i]),
+    "evae_agg_lse": (_i, [_p, _i, _p, _p, _i, _i, _p, _p, _p, _p, _p, _z, _p]),
 }
 
 _lib = None

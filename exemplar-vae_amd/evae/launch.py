@@ -1,7 +1,7 @@
 """The raw-launch layer of the fused training steps (evae/fused_vae.py, evae/fused_std.py) and of the dense autograd operators
 of evae/ops.py: the launcher over the dense entry points of the C ABI, the two job-table fillers, the beta pair (the one pointer
 conversion, vp, is evae/_lib.py's).  No autograd, caller-owned outputs.  The same Launcher also carries the launchers of the
-latent-analysis entry points (tsne_*, nn_rank, pca_*, kmeans_*, cluster_*, silhouette_samples, gmm_*), one method per entry.
+latent-analysis entry points (tsne_*, nn_rank, pca_*, kmeans_*, cluster_*, silhouette_samples, gmm_*, agg_lse), one method per entry.
 
 The fused steps are stage functions over one per-step state object; the modular operators (GatedDenseFn, LinearFn, the heads'
 backward, the deferred weight gradients) are torch.autograd.Functions that build a Launcher where they run.  Every change to
@@ -263,6 +263,11 @@ class Launcher:
 
     def gmm_sample(self, params, d, K, ctype, comp, eps, n, z):
         _lib.check(self.lib.evae_gmm_sample(vp(params), d, int(K), int(ctype), vp(comp), vp(eps), n, vp(z), self.st), "gmm_sample")
+
+    def agg_lse(self, z, B, mean, log_var, N, d, rows, log_q, log_qd, log_cond, ws):
+        """csrc/evae_agg_lse.hip: None switches an output off (rows may be None when log_cond is); the workspace is the caller's"""
+        _lib.check(self.lib.evae_agg_lse(vp(z), B, vp(mean), vp(log_var), N, d, vp(rows), vp(log_q), vp(log_qd), vp(log_cond),
+                                         vp(ws), ws.numel(), self.st), "agg_lse")
 
     def cluster_contingency(self, a, Ka, b, Kb, N, table):
         _lib.check(self.lib.evae_cluster_contingency(vp(a), int(Ka), vp(b), int(Kb), N, vp(table), self.st), "cluster_contingency")

@@ -1344,6 +1344,65 @@ def gmm_sample(params, d, K, covariance_type, comp, eps):
 
 
 # ------------------------------------------------------------------------------------------------
+# Aggregate posterior in fp64 (csrc/evae_agg_lse.hip); the driver is evae/latent_info.py.  Takes what the kernels
+# take and converts nothing.
+# ------------------------------------------------------------------------------------------------
+AggPosteriorLse = collections.namedtuple("AggPosteriorLse", "log_q log_qd log_cond")
+
+
+def agg_lse_max_features():
+    return int(_lib.load().evae_agg_lse_max_features())
+
+
+def agg_lse_max_points():
+    return int(_lib.load().evae_agg_lse_max_points())
+
+
+def agg_lse_tile():
+    """components of one (maximum, sum) pair of the log-sum-exp: a constant of the kernels"""
+    return int(_lib.load().evae_agg_lse_tile())
+
+
+def _agg_rows(name, t):
+    _need_cuda(t)
+    if t.dim() != 2 or t.dtype != torch.float32 or not t.is_contiguous():
+        raise ValueError("agg_posterior_lse: %s must be a contiguous float32 [rows x d] tensor, got %s %s%s"
+                         % (name, t.dtype, tuple(t.shape), "" if t.is_contiguous() else " (strided)"))
+    return t.shape
+
+
+def agg_posterior_lse(z, mean, log_var, rows=None, joint=True, per_dimension=True):
+    """z [B x d], mean and log_var [N x d], all float32 -> AggPosteriorLse(log_q [B], log_qd [B x d], log_cond [B x d]), float64
+    on the device, of q(z) = 1/N sum_j N(z; mean_j, diag exp(log_var_j)): the joint log-density (joint), the log-density of
+    every dimension's marginal (per_dimension) and, with rows int32 [B], log N(z_id; mean_{rows[i] d}, exp(log_var_{rows[i] d})).
+    What is switched off is None.  rows is checked here (one read of its extremes): outside [0, N) is a ValueError."""
+    (B, d), (N, dm) = _agg_rows("z", z), _agg_rows("mean", mean)
+    if tuple(_agg_rows("log_var", log_var)) != (N, dm):
+        raise ValueError("agg_posterior_lse: mean is %s, log_var %s" % (tuple(mean.shape), tuple(log_var.shape)))
+    if d != dm or not 1 <= d <= agg_lse_max_features():
+        raise ValueError("agg_posterior_lse: z has %d features, mean %d (equal and in [1, %d] expected)" % (d, dm, agg_lse_max_features()))
+    cap = agg_lse_max_points()
+    if not 1 <= B <= cap or not 1 <= N <= cap:
+        raise ValueError("agg_posterior_lse: B=%d, N=%d outside [1, %d]" % (B, N, cap))
+    if rows is not None:
+        _need_cuda(rows)
+        if rows.dtype != torch.int32 or not rows.is_contiguous() or tuple(rows.shape) != (B,):
+            raise ValueError("agg_posterior_lse: rows must be a contiguous int32 [%d] tensor, got %s %s" % (B, rows.dtype, tuple(rows.shape)))
+        lo, hi = torch.stack((rows.min(), rows.max())).tolist()
+        if lo < 0 or hi >= N:
+            raise ValueError("agg_posterior_lse: rows span [%d, %d], outside [0, %d)" % (lo, hi, N))
+    if not (joint or per_dimension or rows is not None):
+        raise ValueError("agg_posterior_lse: no output asked for (joint=False, per_dimension=False, rows=None)")
+    dev = z.device
+    log_q = torch.empty(B, dtype=torch.float64, device=dev) if joint else None
+    log_qd = torch.empty((B, d), dtype=torch.float64, device=dev) if per_dimension else None
+    log_cond = torch.empty((B, d), dtype=torch.float64, device=dev) if rows is not None else None
+    ws = torch.empty(_lib.load().evae_agg_lse_workspace_bytes(B, N, d), dtype=torch.uint8, device=dev)
+    launch.Launcher(dev).agg_lse(z, B, mean, log_var, N, d, rows, log_q, log_qd, log_cond, ws)
+    return AggPosteriorLse(log_q, log_qd, log_cond)
+
+
+# ------------------------------------------------------------------------------------------------
 # dense layers
 # ------------------------------------------------------------------------------------------------
 # The launches of this section go through evae/launch.py's Launcher (workspace names, entry points, the probe's names), built

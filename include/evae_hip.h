@@ -1182,6 +1182,38 @@ int evae_gmm_argmax(const double* log_resp /* [N x K] */, int N, int K, int* lab
 int evae_gmm_sample(const double* params, int d, int K, int type, const int* comp /* [n] */, const double* eps /* [n x d] */,
                     int n, float* z /* [n x d] */, evae_stream_t stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Log-density of the aggregate posterior q(z) = 1/N sum_j N(z; mu_j, diag exp(lv_j)) in fp64, jointly and per dimension: what
+ * mutual information, total correlation and the per-dimension KL of the latent code are means of (evae/latent_info.py).
+ * csrc/evae_agg_lse.hip; DESIGN 3.7g.  Inputs are contiguous fp32; every accumulation is fp64 in a fixed order, there is no
+ * atomic, so equal inputs give bit-equal outputs.  No [B x N] buffer exists at any point.
+ *
+ * agg_lse: z [B x d] (queries), mean, log_var [N x d] (components), rows int32 [B] or NULL.  With w_jd = exp(-lv_jd),
+ *   c_jd = -(lv_jd + log 2 pi) / 2 and t_ijd = c_jd - (z_id - mu_jd)^2 w_jd / 2 (the difference taken directly, in fp64):
+ *     log_q[i]       = LSE_j (sum_d t_ijd, d ascending) - log N
+ *     log_qd[i][d]   = LSE_j t_ijd - log N
+ *     log_cond[i][d] = t_{rows[i], d}
+ *   Each output may be NULL; at least one must be asked for, and log_cond needs rows.  rows is the caller's promise (the
+ *   operator evae.ops.agg_posterior_lse checks it before the call); the kernel guards it all the same: an index outside [0, N)
+ *   reads nothing and gives NaN in that row of log_cond.
+ *   The components go in tiles of evae_agg_lse_tile() = 32 in index order: per tile the maximum m and s = sum exp(t - m) in
+ *   index order, and the pairs (m, s) merge in tile order, the side of the larger maximum scaled by exactly 1.  The tile is a
+ *   constant of the kernels: a row's bits depend neither on B, nor on where the row sits in the batch, nor on which other
+ *   outputs are asked for.
+ *   Finite inputs are the caller's contract.  A NaN in z_i makes row i's outputs NaN and reaches no other row; a NaN in a
+ *   component reaches every row (every row's value depends on every component).  Finite inputs give finite outputs.
+ *   1 <= d <= evae_agg_lse_max_features() = 256, 1 <= B, N <= evae_agg_lse_max_points() = 2^20.  ws:
+ *   evae_agg_lse_workspace_bytes(B, N, d) bytes: mu, w, c as fp64 [d x N], written by a prepare launch (the exponentials of
+ *   the log-variances are taken once per call).  Up to four launches: prepare, log_cond, log_q, log_qd.
+ */
+int evae_agg_lse_max_features(void);
+int evae_agg_lse_max_points(void);
+int evae_agg_lse_tile(void);
+size_t evae_agg_lse_workspace_bytes(int B, int N, int d);
+int evae_agg_lse(const float* z /* [B x d] */, int B, const float* mean /* [N x d] */, const float* log_var /* [N x d] */, int N,
+                 int d, const int* rows /* [B] or NULL */, double* log_q /* [B] or NULL */, double* log_qd /* [B x d] or NULL */,
+                 double* log_cond /* [B x d] or NULL */, void* ws, size_t ws_bytes, evae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
