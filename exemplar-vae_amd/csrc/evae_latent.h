@@ -1,5 +1,5 @@
 // The one copy of the blocks the latent-analysis kernels share: evae_tsne_nn.hip, evae_nn_rank.hip, evae_pca.hip,
-// evae_kmeans.hip, evae_gmm.hip, evae_ball_count.hip, evae_agg_lse.hip.  They all rest on one contract -- fp64
+// evae_kmeans.hip, evae_gmm.hip, evae_ball_count.hip, evae_agg_lse.hip, evae_kernel_sum.hip.  They all rest on one contract -- fp64
 // arithmetic on fp32 rows, no floating-point atomics, every sum in a fixed order, equal inputs giving bit-equal outputs -- and this header
 // carries it: nothing here changes the order of a sum, and a helper that would need to know which caller it serves does not
 // belong here.

@@ -311,6 +311,14 @@ SIGNATURES = {
     "evae_agg_lse_tile": (_i, []),
     "evae_agg_lse_workspace_bytes": (_z, [_i, _i, _i]),
     "evae_agg_lse": (_i, [_p, _i, _p, _p, _i, _i, _p, _p, _p, _p, _p, _z, _p]),
+    "evae_kernel_sum_max_features": (_i, []),
+    "evae_kernel_sum_max_points": (_i, []),
+    "evae_kernel_sum_max_degree": (_i, []),
+    "evae_kernel_sum_tile": (_i, []),
+    "evae_kernel_row_sums": (_i, [_p, _i, _p, _i, _i, _i, _d, _d, _i, _i, _p, _p]),
+    "evae_ordered_sum": (_i, [_p, _i, _p, _p]),
+    "evae_sym_congruence_workspace_bytes": (_z, [_i]),
+    "evae_sym_congruence": (_i, [_p, _p, _p, _i, _p, _z, _p]),
 }
 
 _lib = None

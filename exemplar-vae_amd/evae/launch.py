@@ -1,7 +1,7 @@
 """The raw-launch layer of the fused training steps (evae/fused_vae.py, evae/fused_std.py) and of the dense autograd operators
 of evae/ops.py: the launcher over the dense entry points of the C ABI, the two job-table fillers, the beta pair (the one pointer
 conversion, vp, is evae/_lib.py's).  No autograd, caller-owned outputs.  The same Launcher also carries the launchers of the
-latent-analysis entry points (tsne_*, nn_rank, pca_*, kmeans_*, cluster_*, silhouette_samples, gmm_*, agg_lse), one method per entry.
+latent-analysis entry points (tsne_*, nn_rank, pca_*, kmeans_*, cluster_*, silhouette_samples, gmm_*, agg_lse, kernel_row_sums, ordered_sum, sym_congruence), one method per entry.
 
 The fused steps are stage functions over one per-step state object; the modular operators (GatedDenseFn, LinearFn, the heads'
 backward, the deferred weight gradients) are torch.autograd.Functions that build a Launcher where they run.  Every change to
@@ -268,6 +268,17 @@ class Launcher:
         """csrc/evae_agg_lse.hip: None switches an output off (rows may be None when log_cond is); the workspace is the caller's"""
         _lib.check(self.lib.evae_agg_lse(vp(z), B, vp(mean), vp(log_var), N, d, vp(rows), vp(log_q), vp(log_qd), vp(log_cond),
                                          vp(ws), ws.numel(), self.st), "agg_lse")
+
+    # kernel sums in fp64 (csrc/evae_kernel_sum.hip): outputs and the workspace are the caller's
+    def kernel_row_sums(self, q, B, c, N, d, kind, gamma, coef0, degree, skip_self, row_sum):
+        _lib.check(self.lib.evae_kernel_row_sums(vp(q), B, vp(c), N, d, int(kind), float(gamma), float(coef0), int(degree),
+                                                 int(bool(skip_self)), vp(row_sum), self.st), "kernel_row_sums")
+
+    def ordered_sum(self, x, n, out):
+        _lib.check(self.lib.evae_ordered_sum(vp(x), n, vp(out), self.st), "ordered_sum")
+
+    def sym_congruence(self, A, S, out, d, ws):
+        _lib.check(self.lib.evae_sym_congruence(vp(A), vp(S), vp(out), d, vp(ws), ws.numel(), self.st), "sym_congruence")
 
     def cluster_contingency(self, a, Ka, b, Kb, N, table):
         _lib.check(self.lib.evae_cluster_contingency(vp(a), int(Ka), vp(b), int(Kb), N, vp(table), self.st), "cluster_contingency")

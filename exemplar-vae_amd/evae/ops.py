@@ -1403,6 +1403,113 @@ def agg_posterior_lse(z, mean, log_var, rows=None, joint=True, per_dimension=Tru
 
 
 # ------------------------------------------------------------------------------------------------
+# Kernel sums in fp64 (csrc/evae_kernel_sum.hip); the driver is evae/sample_quality.py (kernel_mmd,
+# frechet_distance).  Rows are taken as float32 (converted like pca_moments does); the fp64 operands are converted by nobody.
+# ------------------------------------------------------------------------------------------------
+KERNEL_KINDS = {'poly': 0, 'rbf': 1}     # EVAE_KERNEL_POLY, EVAE_KERNEL_RBF
+
+
+def kernel_sum_tile():
+    """columns of one tile of kernel_row_sums: a tile's terms are added in index order, the tiles in order; a constant"""
+    return int(_lib.load().evae_kernel_sum_tile())
+
+
+def kernel_sum_max_features():
+    return int(_lib.load().evae_kernel_sum_max_features())
+
+
+def kernel_sum_max_points():
+    return int(_lib.load().evae_kernel_sum_max_points())
+
+
+def kernel_sum_max_degree():
+    return int(_lib.load().evae_kernel_sum_max_degree())
+
+
+def kernel_sum_check(kind, degree, coef0, who, name="kind"):
+    """the kernel's own arguments, checked without a tensor in sight (kernel_mmd asks before it launches anything): a kind
+    that is not 'poly' or 'rbf', and for 'poly' a degree that is not an integer in [1, kernel_sum_max_degree()] or a coef0
+    that is not a number, are ValueErrors"""
+    if kind not in KERNEL_KINDS:
+        raise ValueError("%s: %s=%r, 'poly' or 'rbf' expected" % (who, name, kind))
+    if kind != 'poly':
+        return
+    top = kernel_sum_max_degree()
+    if isinstance(degree, bool) or not isinstance(degree, (int, float)) or degree != int(degree) or not 1 <= degree <= top:
+        raise ValueError("%s: degree=%r, an integer in [1, %d] expected" % (who, degree, top))
+    if isinstance(coef0, bool) or not isinstance(coef0, (int, float)):
+        raise ValueError("%s: coef0=%r, a number expected" % (who, coef0))
+
+
+def _ks_rows(name, t):
+    _need_cuda(t)
+    if t.dim() != 2 or not t.is_floating_point():
+        raise ValueError("kernel_row_sums: %s must be a floating-point [rows x d] tensor, got %s %s" % (name, t.dtype, tuple(t.shape)))
+    return _f32(t)
+
+
+def kernel_row_sums(q, c, kind='poly', gamma=None, coef0=1.0, degree=3, skip_self=False):
+    """q [B x d], c [N x d] -> float64 [B]: row_sum[i] = sum_j k(q_i, c_j) in fp64, j ascending (tiles of kernel_sum_tile()
+    columns, a tile's terms in index order, the tiles in order).  kind 'poly': (gamma <q_i, c_j> + coef0)^degree, degree an
+    integer in [1, 8]; 'rbf': exp(-gamma |q_i - c_j|^2) from direct differences.  gamma=None: 1 / d.  skip_self (the
+    within-set form, B == N) leaves the term j == i out by index.  Equal inputs give bit-equal outputs; a row's bits do not
+    depend on the batch it is in.  d <= kernel_sum_max_features() = 256: the kernel keeps a wave's 64 query rows in LDS whole
+    (d x 256 bytes beside the staged columns); wider rows, the 784 pixels for one, would need the query staged in chunks of
+    features as the columns are, which this kernel does not do."""
+    q, c = _ks_rows("q", q), _ks_rows("c", c)
+    (B, d), (N, dc) = q.shape, c.shape
+    if d != dc:
+        raise ValueError("kernel_row_sums: q has %d features, c %d" % (d, dc))
+    if not 1 <= d <= kernel_sum_max_features():
+        raise ValueError("kernel_row_sums: q and c have %d features, outside [1, %d]" % (d, kernel_sum_max_features()))
+    cap = kernel_sum_max_points()
+    if not 1 <= B <= cap:
+        raise ValueError("kernel_row_sums: q has %d rows, outside [1, %d]" % (B, cap))
+    if not 1 <= N <= cap:
+        raise ValueError("kernel_row_sums: c has %d rows, outside [1, %d]" % (N, cap))
+    kernel_sum_check(kind, degree, coef0, "kernel_row_sums")
+    if skip_self and B != N:
+        raise ValueError("kernel_row_sums: skip_self with %d rows in q and %d in c (the within-set form needs B == N)" % (B, N))
+    if gamma is not None and (isinstance(gamma, bool) or not isinstance(gamma, (int, float))):
+        raise ValueError("kernel_row_sums: gamma=%r, a number or None (1 / d) expected" % (gamma,))
+    gamma = 1.0 / d if gamma is None else float(gamma)
+    row_sum = torch.empty(B, dtype=torch.float64, device=q.device)
+    launch.Launcher(q.device).kernel_row_sums(q, B, c, N, d, KERNEL_KINDS[kind], gamma, coef0, int(degree) if kind == 'poly' else 1,
+                                              skip_self, row_sum)
+    return row_sum
+
+
+def ordered_sum(x):
+    """x float64 [n] -> float64 0-d tensor on the device: x[0] + x[1] + .. from left to right, one workgroup, bit-reproducible"""
+    _need_cuda(x)
+    if x.dim() != 1 or x.dtype != torch.float64 or not x.is_contiguous():
+        raise ValueError("ordered_sum: x must be a contiguous float64 [n] tensor, got %s %s" % (x.dtype, tuple(x.shape)))
+    n = x.shape[0]
+    if not 1 <= n <= kernel_sum_max_points():
+        raise ValueError("ordered_sum: x has %d entries, outside [1, %d]" % (n, kernel_sum_max_points()))
+    out = torch.empty(1, dtype=torch.float64, device=x.device)
+    launch.Launcher(x.device).ordered_sum(x, n, out)
+    return out[0]
+
+
+def sym_congruence(A, S):
+    """A, S float64 [d x d], S symmetric -> A S A^T float64 [d x d], symmetric bit for bit: T = A S, then T A^T, every entry's
+    sum in ascending index; d <= kernel_sum_max_features()"""
+    _need_cuda(A, S)
+    if A.dim() != 2 or A.shape[0] != A.shape[1] or A.dtype != torch.float64 or not A.is_contiguous():
+        raise ValueError("sym_congruence: A must be a contiguous float64 [d x d] tensor, got %s %s" % (A.dtype, tuple(A.shape)))
+    d = A.shape[0]
+    if not 1 <= d <= kernel_sum_max_features():
+        raise ValueError("sym_congruence: A is [%d x %d], d outside [1, %d]" % (d, d, kernel_sum_max_features()))
+    if tuple(S.shape) != (d, d) or S.dtype != torch.float64 or not S.is_contiguous():
+        raise ValueError("sym_congruence: S must be a contiguous float64 [%d x %d] tensor, got %s %s" % (d, d, S.dtype, tuple(S.shape)))
+    out = torch.empty((d, d), dtype=torch.float64, device=A.device)
+    ws = torch.empty(_lib.load().evae_sym_congruence_workspace_bytes(d), dtype=torch.uint8, device=A.device)
+    launch.Launcher(A.device).sym_congruence(A, S, out, d, ws)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 # dense layers
 # ------------------------------------------------------------------------------------------------
 # The launches of this section go through evae/launch.py's Launcher (workspace names, entry points, the probe's names), built

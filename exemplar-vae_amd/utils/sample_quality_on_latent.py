@@ -26,13 +26,17 @@ def report_sample_quality(train_loader, test_loader, model, dir, args):
     means q(z|x) of all three sets; 'pixel': flattened images; 'both'), sample_quality_k (default 5), sample_quality_save
     (default 0).  Writes sample_quality.json under `dir`: one object per space with precision, recall, density, coverage,
     authenticity, nearest_distance_median, nearest_k, n_real, n_fake, n_train.  With sample_quality_save also
-    sample_quality_nearest.npy, int32 [samples]: the training row nearest to every sample in the (first) space scored.  Prints
+    sample_quality_nearest.npy, int32 [samples]: the training row nearest to every sample in the (first) space scored.  With
+    sample_quality_distances (default False) every space also gets frechet_distance, kid (against the test split) and kid_train
+    (against the training split), each where the device kernels take the space's width: the 784 pixels are wider than both
+    caps (256), so the pixel space keeps its ball counts only; the latent space gets all three.  Prints
     one line and returns the dict that was written."""
     spaces = _SPACES.get(getattr(args, 'sample_quality_space', None) or 'latent')
     if spaces is None:
         raise ValueError("sample_quality_space=%r: 'latent', 'pixel' or 'both' expected" % (args.sample_quality_space,))
     B = int(args.batch_size)
     k = int(getattr(args, 'sample_quality_k', None) or 5)
+    distances = bool(getattr(args, 'sample_quality_distances', False))
     train_x = _full_batches(extract_full_data(train_loader)[0], B).to(args.device)
     test_x = _full_batches(extract_full_data(test_loader)[0], B).to(args.device)
     count = getattr(args, 'sample_quality_samples', None)
@@ -55,7 +59,7 @@ def report_sample_quality(train_loader, test_loader, model, dir, args):
             sets['pixel'] = tuple(x.reshape(len(x), -1).float() for x in (train_x, test_x, fake_x))
         for space in spaces:
             train, test, fake = sets[space]
-            report[space] = dict(sample_quality(test, fake, nearest_k=k, train=train), n_train=int(len(train)))
+            report[space] = dict(sample_quality(test, fake, nearest_k=k, train=train, distances=distances), n_train=int(len(train)))
         nearest = nearest_real(sets[spaces[0]][0], sets[spaces[0]][2])[0] if getattr(args, 'sample_quality_save', 0) else None
     model.train(was_training)
     os.makedirs(dir, exist_ok=True)

@@ -1214,6 +1214,42 @@ int evae_agg_lse(const float* z /* [B x d] */, int B, const float* mean /* [N x 
                  int d, const int* rows /* [B] or NULL */, double* log_q /* [B] or NULL */, double* log_qd /* [B x d] or NULL */,
                  double* log_cond /* [B x d] or NULL */, void* ws, size_t ws_bytes, evae_stream_t stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Kernel sums in fp64: what the kernel MMD^2 of two sets of rows (KID with the cubic kernel) is made of, and the two small
+ * pieces the Frechet distance needs beside the PCA entries (evae/sample_quality.py).  csrc/evae_kernel_sum.hip; DESIGN 3.7h.
+ * Rows are contiguous fp32 (4-byte alignment is enough); every accumulation is fp64 in a fixed order, there is no atomic, so
+ * equal inputs give bit-equal outputs.  No [B x N] buffer exists at any point.
+ *
+ * kernel_row_sums: q [B x d], c [N x d] -> row_sum[i] = sum_j k(q_i, c_j), j ascending.  skip_self (needs B == N: q and c are
+ *   the same set) leaves the term j == i out, by index, not by value: a duplicate row elsewhere is still counted.
+ *     EVAE_KERNEL_POLY: k = (gamma <q_i, c_j> + coef0)^degree, 1 <= degree <= evae_kernel_sum_max_degree() = 8; the dot product
+ *       by fma in ascending feature order (the products of fp32 entries are exact in fp64), fma(gamma, dot, coef0), the power
+ *       by degree - 1 multiplications from the left.  KID: gamma = 1 / d, coef0 = 1, degree = 3.
+ *     EVAE_KERNEL_RBF:  k = exp(-gamma |q_i - c_j|^2), the differences taken directly in fp64, features ascending (degree
+ *       and coef0 are not read).
+ *   The columns go in tiles of evae_kernel_sum_tile() = 32 in index order: a tile's terms are added in index order, the tile
+ *   sums in tile order.  The tile is a constant of the kernel: a row's bits depend neither on B, nor on where the row sits in
+ *   the batch, nor on the grid.  Nothing is read past the end of c: a tile's slots past N are left out by index.
+ *   A NaN or inf in q_i stays in row_sum[i]; one in c_j reaches every row (every row's sum has that term).  Nothing faults.
+ *   1 <= d <= evae_kernel_sum_max_features() = 256, 1 <= B, N <= evae_kernel_sum_max_points() = 2^20.  One launch.
+ * ordered_sum: out[0] = x[0] + x[1] + .. + x[n - 1] from left to right, one workgroup; 1 <= n <= 2^20.
+ * sym_congruence: out = A S A^T, all fp64 [d x d], d <= 256: T = A S into ws (evae_sym_congruence_workspace_bytes(d) bytes),
+ *   then T A^T, every entry's sum by fma in ascending index; out[i][j] and out[j][i] are written from the one value computed
+ *   for i <= j, so the result is symmetric bit for bit (S is taken as symmetric).  out must not overlap A or S, nor ws any of the three (refused).  Two launches.
+ */
+#define EVAE_KERNEL_POLY 0
+#define EVAE_KERNEL_RBF 1
+int evae_kernel_sum_max_features(void);
+int evae_kernel_sum_max_points(void);
+int evae_kernel_sum_max_degree(void);
+int evae_kernel_sum_tile(void);
+int evae_kernel_row_sums(const float* q /* [B x d] */, int B, const float* c /* [N x d] */, int N, int d, int kind, double gamma,
+                         double coef0, int degree, int skip_self, double* row_sum /* [B] */, evae_stream_t stream);
+int evae_ordered_sum(const double* x /* [n] */, int n, double* out /* [1] */, evae_stream_t stream);
+size_t evae_sym_congruence_workspace_bytes(int d);
+int evae_sym_congruence(const double* A /* [d x d] */, const double* S /* [d x d] */, double* out /* [d x d] */, int d, void* ws,
+                        size_t ws_bytes, evae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
