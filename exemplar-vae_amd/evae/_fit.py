@@ -1,4 +1,4 @@
-"""What the iterated drivers (evae/cluster.py's KMeans, evae/mixture.py's GaussianMixture) share: how an input becomes rows on
+"""What the iterated drivers (evae/cluster.py's KMeans, evae/mixture.py's GaussianMixture, evae/linear.py's LogisticRegression) share: how an input becomes rows on
 the device, the generator behind random_state, and the loop that issues steps blind and reads the device's record once per
 batch.  Private to the package."""
 import numpy as np

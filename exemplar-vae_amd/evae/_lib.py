@@ -319,6 +319,23 @@ SIGNATURES = {
     "evae_ordered_sum": (_i, [_p, _i, _p, _p]),
     "evae_sym_congruence_workspace_bytes": (_z, [_i]),
     "evae_sym_congruence": (_i, [_p, _p, _p, _i, _p, _z, _p]),
+    "evae_logreg_max_classes": (_i, []),
+    "evae_logreg_max_features": (_i, []),
+    "evae_logreg_max_points": (_i, []),
+    "evae_logreg_max_history": (_i, []),
+    "evae_logreg_max_line_steps": (_i, []),
+    "evae_logreg_chunk_rows": (_i, []),
+    "evae_logreg_max_bytes": (_z, []),
+    "evae_logreg_solver_doubles": (_z, [_i, _i, _i, _i]),
+    "evae_logreg_workspace_bytes": (_z, [_i, _i, _i, _i, _i]),
+    "evae_logreg_logits": (_i, [_p, _i, _i, _p, _i, _i, _p, _p]),
+    "evae_logreg_line": (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _p, _i, _d, _i, _p, _p, _i, _p, _z, _p]),
+    "evae_logreg_grad": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _z, _p]),
+    "evae_logreg_finish": (_i, [_i, _i, _i, _i, _i, _p, _p, _i, _d, _d, _p, _p, _z, _p]),
+    "evae_logreg_direction": (_i, [_p, _i, _i, _i, _i, _p, _p]),
+    "evae_logreg_begin": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _i, _d, _d, _i, _p, _p, _z, _p]),
+    "evae_logreg_step": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _i, _d, _d, _i, _p, _p, _i, _p, _z, _p]),
+    "evae_logreg_softmax": (_i, [_p, _i, _i, _p, _p, _p]),
 }
 
 _lib = None

@@ -1,7 +1,7 @@
 """The raw-launch layer of the fused training steps (evae/fused_vae.py, evae/fused_std.py) and of the dense autograd operators
 of evae/ops.py: the launcher over the dense entry points of the C ABI, the two job-table fillers, the beta pair (the one pointer
 conversion, vp, is evae/_lib.py's).  No autograd, caller-owned outputs.  The same Launcher also carries the launchers of the
-latent-analysis entry points (tsne_*, nn_rank, pca_*, kmeans_*, cluster_*, silhouette_samples, gmm_*, agg_lse, kernel_row_sums, ordered_sum, sym_congruence), one method per entry.
+latent-analysis entry points (tsne_*, nn_rank, pca_*, kmeans_*, cluster_*, silhouette_samples, gmm_*, agg_lse, kernel_row_sums, ordered_sum, sym_congruence, logreg_*), one method per entry.
 
 The fused steps are stage functions over one per-step state object; the modular operators (GatedDenseFn, LinearFn, the heads'
 backward, the deferred weight gradients) are torch.autograd.Functions that build a Launcher where they run.  Every change to
@@ -279,6 +279,40 @@ class Launcher:
 
     def sym_congruence(self, A, S, out, d, ws):
         _lib.check(self.lib.evae_sym_congruence(vp(A), vp(S), vp(out), d, vp(ws), ws.numel(), self.st), "sym_congruence")
+
+    # linear probe in fp64 (csrc/evae_logreg.hip): every buffer and workspace is the caller's
+    def logreg_logits(self, x, N, d, W, K, fit_intercept, out):
+        _lib.check(self.lib.evae_logreg_logits(vp(x), N, d, vp(W), int(K), int(fit_intercept), vp(out), self.st), "logreg_logits")
+
+    def logreg_line(self, Z, ZD, y, N, d, K, fit_intercept, W, solver, history, lam, line_steps, state, ring, ws):
+        _lib.check(self.lib.evae_logreg_line(vp(Z), vp(ZD), vp(y), N, d, int(K), int(fit_intercept), vp(W), vp(solver), int(history),
+                                             float(lam), int(line_steps), vp(state), vp(ring), 0 if ring is None else ring.numel(),
+                                             vp(ws), ws.numel(), self.st), "logreg_line")
+
+    def logreg_grad(self, x, y, N, d, K, fit_intercept, line_steps, Z, ZD, state, ws):
+        _lib.check(self.lib.evae_logreg_grad(vp(x), vp(y), N, d, int(K), int(fit_intercept), int(line_steps), vp(Z), vp(ZD), vp(state),
+                                             vp(ws), ws.numel(), self.st), "logreg_grad")
+
+    def logreg_finish(self, N, d, K, fit_intercept, line_steps, W, solver, history, lam, tol, state, ws):
+        _lib.check(self.lib.evae_logreg_finish(N, d, int(K), int(fit_intercept), int(line_steps), vp(W), vp(solver), int(history),
+                                               float(lam), float(tol), vp(state), vp(ws), ws.numel(), self.st), "logreg_finish")
+
+    def logreg_direction(self, solver, d, K, fit_intercept, history, state):
+        _lib.check(self.lib.evae_logreg_direction(vp(solver), d, int(K), int(fit_intercept), int(history), vp(state), self.st),
+                   "logreg_direction")
+
+    def logreg_begin(self, x, y, N, d, K, fit_intercept, W, Z, ZD, solver, history, lam, tol, line_steps, state, ws):
+        _lib.check(self.lib.evae_logreg_begin(vp(x), vp(y), N, d, int(K), int(fit_intercept), vp(W), vp(Z), vp(ZD), vp(solver),
+                                              int(history), float(lam), float(tol), int(line_steps), vp(state), vp(ws), ws.numel(),
+                                              self.st), "logreg_begin")
+
+    def logreg_step(self, x, y, N, d, K, fit_intercept, W, Z, ZD, solver, history, lam, tol, line_steps, state, ring, ws):
+        _lib.check(self.lib.evae_logreg_step(vp(x), vp(y), N, d, int(K), int(fit_intercept), vp(W), vp(Z), vp(ZD), vp(solver),
+                                             int(history), float(lam), float(tol), int(line_steps), vp(state), vp(ring),
+                                             0 if ring is None else ring.numel(), vp(ws), ws.numel(), self.st), "logreg_step")
+
+    def logreg_softmax(self, Z, N, K, logp, labels):
+        _lib.check(self.lib.evae_logreg_softmax(vp(Z), N, int(K), vp(logp), vp(labels), self.st), "logreg_softmax")
 
     def cluster_contingency(self, a, Ka, b, Kb, N, table):
         _lib.check(self.lib.evae_cluster_contingency(vp(a), int(Ka), vp(b), int(Kb), N, vp(table), self.st), "cluster_contingency")

@@ -1510,6 +1510,249 @@ def sym_congruence(A, S):
 
 
 # ------------------------------------------------------------------------------------------------
+# Linear probe in fp64 (csrc/evae_logreg.hip); the driver is evae/linear.py.  Like the gmm_* entries these take
+# what the kernels take and convert nothing.  The vectors of the solver live in ONE float64 buffer (logreg_solver) that
+# logreg_views slices without copying; W is [K x p] with the intercept column last (p = d + 1, or d without an intercept).
+# ------------------------------------------------------------------------------------------------
+LOGREG_STATE = 8     # the record: iterations, done, converged, f, t, j, line search failed, G.D
+
+
+def logreg_max_classes():
+    return int(_lib.load().evae_logreg_max_classes())
+
+
+def logreg_max_features():
+    return int(_lib.load().evae_logreg_max_features())
+
+
+def logreg_max_points():
+    return int(_lib.load().evae_logreg_max_points())
+
+
+def logreg_max_history():
+    return int(_lib.load().evae_logreg_max_history())
+
+
+def logreg_max_line_steps():
+    return int(_lib.load().evae_logreg_max_line_steps())
+
+
+def logreg_chunk_rows():
+    """rows whose losses and gradient sums are formed together"""
+    return int(_lib.load().evae_logreg_chunk_rows())
+
+
+def logreg_max_bytes():
+    """Z and Z_D plus workspace may not exceed this"""
+    return int(_lib.load().evae_logreg_max_bytes())
+
+
+def logreg_workspace_bytes(N, d, K, fit_intercept, line_steps):
+    return int(_lib.load().evae_logreg_workspace_bytes(int(N), int(d), int(K), int(bool(fit_intercept)), int(line_steps)))
+
+
+def logreg_check_sizes(N, d, K, fit_intercept, history, line_steps, who):
+    """what the kernels refuse, from the sizes alone: before any allocation or launch (N None: the shape of W only)"""
+    if not 2 <= K <= logreg_max_classes():
+        raise _lib.EvaeError("%s: K=%d outside [2, %d]" % (who, K, logreg_max_classes()))
+    if not 1 <= d <= logreg_max_features():
+        raise _lib.EvaeError("%s: %d features outside [1, %d]" % (who, d, logreg_max_features()))
+    if not 1 <= history <= logreg_max_history():
+        raise _lib.EvaeError("%s: history=%d outside [1, %d]" % (who, history, logreg_max_history()))
+    if not 1 <= line_steps <= logreg_max_line_steps():
+        raise _lib.EvaeError("%s: line_steps=%d outside [1, %d]" % (who, line_steps, logreg_max_line_steps()))
+    if N is None:
+        return
+    if not 1 <= N <= logreg_max_points():
+        raise _lib.EvaeError("%s: N=%d outside [1, %d]" % (who, N, logreg_max_points()))
+    z, ws = 8 * N * K, logreg_workspace_bytes(N, d, K, fit_intercept, line_steps)
+    if 2 * z + ws > logreg_max_bytes():
+        raise _lib.EvaeError("%s: Z and Z_D of %d bytes each plus a workspace of %d bytes for N=%d, d=%d, K=%d exceed %d bytes"
+                             % (who, z, ws, N, d, K, logreg_max_bytes()))
+
+
+def _logreg_p(d, fit_intercept):
+    return int(d) + (1 if fit_intercept else 0)
+
+
+def logreg_solver(d, K, fit_intercept, history, device):
+    """a zeroed solver buffer (float64) for these sizes"""
+    logreg_check_sizes(None, d, K, fit_intercept, history, 1, "logreg_solver")
+    n = _lib.load().evae_logreg_solver_doubles(int(d), int(K), int(bool(fit_intercept)), int(history))
+    return torch.zeros(n, dtype=torch.float64, device=device)
+
+
+def logreg_views(solver, d, K, fit_intercept, history):
+    """-> dict of views into a solver buffer: G, Q, D [K x p]; S, Y [m x K x p]; sy, yy, alpha [m]; scal [8] (pairs held, next
+    slot, max|G| / N, ww)"""
+    p, m = _logreg_p(d, fit_intercept), int(history)
+    L = K * p
+    o = 3 * L + 2 * m * L
+    return dict(G=solver[0:L].view(K, p), Q=solver[L:2 * L].view(K, p), D=solver[2 * L:3 * L].view(K, p),
+                S=solver[3 * L:3 * L + m * L].view(m, K, p), Y=solver[3 * L + m * L:o].view(m, K, p), sy=solver[o:o + m],
+                yy=solver[o + m:o + 2 * m], alpha=solver[o + 2 * m:o + 3 * m], scal=solver[o + 3 * m:o + 3 * m + 8])
+
+
+def logreg_workspace(N, d, K, fit_intercept, line_steps, device):
+    """the one workspace of the logreg_* entries for these sizes (a uint8 tensor)"""
+    return torch.empty(logreg_workspace_bytes(N, d, K, fit_intercept, line_steps), dtype=torch.uint8, device=device)
+
+
+def logreg_workspace_views(ws, N, d, K, fit_intercept, line_steps):
+    """-> dict of float64 views into a workspace: partial [chunks x K x p] (the gradient sums of the chunks), loss [chunks],
+    line [chunks x line_steps] (the trial losses of the chunks); each part starts on a 256-byte boundary"""
+    p, chunks = _logreg_p(d, fit_intercept), (N + logreg_chunk_rows() - 1) // logreg_chunk_rows()
+    up = lambda b: (b + 255) // 256 * 256
+    o1 = up(8 * chunks * K * p)
+    o2 = o1 + up(8 * chunks)
+    f = ws.view(torch.float64) if ws.numel() % 8 == 0 else ws[:ws.numel() // 8 * 8].view(torch.float64)
+    return dict(partial=f[0:chunks * K * p].view(chunks, K, p), loss=f[o1 // 8:o1 // 8 + chunks],
+                line=f[o2 // 8:o2 // 8 + chunks * line_steps].view(chunks, line_steps))
+
+
+def logreg_state(device):
+    """a zeroed record for logreg_begin / logreg_step"""
+    return torch.zeros(LOGREG_STATE, dtype=torch.float64, device=device)
+
+
+def logreg_check_labels(y, K, who):
+    """y int32 [N] on the device: a label outside [0, K) is refused here (one read of two numbers), never met by a kernel"""
+    lo, hi = int(y.min().item()), int(y.max().item())
+    if lo < 0 or hi >= K:
+        raise _lib.EvaeError("%s: labels in [%d, %d], outside [0, %d)" % (who, lo, hi, K))
+
+
+def _logreg_w(name, W, d, fit_intercept, who):
+    _need_cuda(W)
+    if W.dim() != 2:
+        raise _lib.EvaeError("%s: %s must be [K x p], got %s" % (who, name, tuple(W.shape)))
+    K = W.shape[0]
+    _dev_tensor(name, W, torch.float64, (K, _logreg_p(d, fit_intercept)), who)
+    return K
+
+
+def _logreg_solver(solver, d, K, fit_intercept, history, who):
+    n = _lib.load().evae_logreg_solver_doubles(int(d), int(K), int(bool(fit_intercept)), int(history))
+    _dev_tensor("solver", solver, torch.float64, (n,), who)
+
+
+def logreg_logits(x, W, fit_intercept=True, out=None):
+    """x [N x d] float32, W float64 [K x p] -> float64 [N x K]: x_n . w_k by fma in feature order, the intercept last"""
+    N, d = _dev_rows("x", x, "logreg_logits", logreg_max_features(), logreg_max_points())
+    K = _logreg_w("W", W, d, fit_intercept, "logreg_logits")
+    logreg_check_sizes(None, d, K, fit_intercept, 1, 1, "logreg_logits")
+    out = torch.empty((N, K), dtype=torch.float64, device=x.device) if out is None else out
+    _dev_tensor("out", out, torch.float64, (N, K), "logreg_logits")
+    launch.Launcher(x.device).logreg_logits(x, N, d, W, K, bool(fit_intercept), out)
+    return out
+
+
+def _logreg_zs(Z, ZD, y, who, labels_checked):
+    _need_cuda(Z)
+    if Z.dim() != 2:
+        raise _lib.EvaeError("%s: Z must be [N x K], got %s" % (who, tuple(Z.shape)))
+    N, K = Z.shape
+    _dev_tensor("Z", Z, torch.float64, (N, K), who)
+    _dev_tensor("ZD", ZD, torch.float64, (N, K), who)
+    _dev_tensor("y", y, torch.int32, (N,), who)
+    if not labels_checked:
+        logreg_check_labels(y, K, who)
+    return N, K
+
+
+def logreg_line(Z, ZD, y, W, d, fit_intercept, solver, history, lam, line_steps, state, ring, ws, labels_checked=False):
+    """The line launch: from Z, Z_D, W, the solver's D, state[3] = f and state[7] = G.D the first t = 2^-j, j < line_steps, with
+    f(W + t D) <= f + 1e-4 t G.D -> state[4] = t, state[5] = j, ring[state[0]] = j, W += t D in place; none: state[6] = state[1]
+    = 1 and W as it was.  The chunks' trial losses stay in the workspace (logreg_workspace_views)."""
+    N, K = _logreg_zs(Z, ZD, y, "logreg_line", labels_checked)
+    logreg_check_sizes(N, d, K, fit_intercept, history, line_steps, "logreg_line")
+    _logreg_w("W", W, d, fit_intercept, "logreg_line")
+    _logreg_solver(solver, d, K, fit_intercept, history, "logreg_line")
+    _dev_tensor("state", state, torch.float64, (LOGREG_STATE,), "logreg_line")
+    if ring is not None:
+        _dev_tensor("ring", ring, torch.int32, (ring.numel(),), "logreg_line")
+    _need_cuda(ws)
+    launch.Launcher(Z.device).logreg_line(Z, ZD, y, N, int(d), K, bool(fit_intercept), W, solver, history, lam, line_steps, state,
+                                          ring, ws)
+
+
+def logreg_grad(x, y, Z, ZD, fit_intercept, line_steps, state, ws, labels_checked=False):
+    """The gradient launch: Z += state[4] Z_D in place, R = softmax(Z) - onehot(y) into Z_D, the chunks' sums of R_nk a_nc and
+    losses into the workspace"""
+    N, d = _dev_rows("x", x, "logreg_grad", logreg_max_features(), logreg_max_points())
+    N2, K = _logreg_zs(Z, ZD, y, "logreg_grad", labels_checked)
+    if N2 != N:
+        raise _lib.EvaeError("logreg_grad: x has %d rows, Z %d" % (N, N2))
+    logreg_check_sizes(N, d, K, fit_intercept, 1, line_steps, "logreg_grad")
+    _dev_tensor("state", state, torch.float64, (LOGREG_STATE,), "logreg_grad")
+    _need_cuda(ws)
+    launch.Launcher(x.device).logreg_grad(x, y, N, d, K, bool(fit_intercept), line_steps, Z, ZD, state, ws)
+
+
+def logreg_finish(N, d, W, fit_intercept, solver, history, lam, tol, line_steps, state, ws):
+    """The finish launch: G from the workspace's chunk sums and lam W, the pair, f, the stop, the next D and G.D"""
+    K = _logreg_w("W", W, d, fit_intercept, "logreg_finish")
+    logreg_check_sizes(N, d, K, fit_intercept, history, line_steps, "logreg_finish")
+    _logreg_solver(solver, d, K, fit_intercept, history, "logreg_finish")
+    _dev_tensor("state", state, torch.float64, (LOGREG_STATE,), "logreg_finish")
+    _need_cuda(ws)
+    launch.Launcher(W.device).logreg_finish(int(N), int(d), K, bool(fit_intercept), line_steps, W, solver, history, lam, tol, state, ws)
+
+
+def logreg_direction(solver, d, K, fit_intercept, history, state):
+    """D = -H G by the two-loop recursion over the pairs in the solver, and state[7] = G.D"""
+    logreg_check_sizes(None, d, int(K), fit_intercept, history, 1, "logreg_direction")
+    _logreg_solver(solver, d, K, fit_intercept, history, "logreg_direction")
+    _dev_tensor("state", state, torch.float64, (LOGREG_STATE,), "logreg_direction")
+    launch.Launcher(solver.device).logreg_direction(solver, int(d), int(K), bool(fit_intercept), history, state)
+
+
+def _logreg_fit_args(x, y, W, Z, ZD, fit_intercept, solver, history, line_steps, state, ws, who, labels_checked):
+    N, d = _dev_rows("x", x, who, logreg_max_features(), logreg_max_points())
+    K = _logreg_w("W", W, d, fit_intercept, who)
+    logreg_check_sizes(N, d, K, fit_intercept, history, line_steps, who)
+    _dev_tensor("Z", Z, torch.float64, (N, K), who)
+    _dev_tensor("ZD", ZD, torch.float64, (N, K), who)
+    _dev_tensor("y", y, torch.int32, (N,), who)
+    _logreg_solver(solver, d, K, fit_intercept, history, who)
+    _dev_tensor("state", state, torch.float64, (LOGREG_STATE,), who)
+    _need_cuda(ws)
+    if not labels_checked:
+        logreg_check_labels(y, K, who)
+    return N, d, K
+
+
+def logreg_begin(x, y, W, Z, ZD, fit_intercept, solver, history, lam, tol, line_steps, state, ws, labels_checked=False):
+    """state, solver and the workspace's ticket zeroed, then Z = logits(W), the gradient, f and the first direction at W"""
+    N, d, K = _logreg_fit_args(x, y, W, Z, ZD, fit_intercept, solver, history, line_steps, state, ws, "logreg_begin", labels_checked)
+    launch.Launcher(x.device).logreg_begin(x, y, N, d, K, bool(fit_intercept), W, Z, ZD, solver, history, lam, tol, line_steps, state, ws)
+
+
+def logreg_step(x, y, W, Z, ZD, fit_intercept, solver, history, lam, tol, line_steps, state, ring, ws, labels_checked=False):
+    """One L-BFGS iteration in place (logits of D, line, gradient, finish: four launches on the current stream), after
+    logreg_begin with the same buffers.  Once state[1] (done) is set, further calls change nothing: a caller may issue several
+    and read the record once."""
+    N, d, K = _logreg_fit_args(x, y, W, Z, ZD, fit_intercept, solver, history, line_steps, state, ws, "logreg_step", labels_checked)
+    if ring is not None:
+        _dev_tensor("ring", ring, torch.int32, (ring.numel(),), "logreg_step")
+    launch.Launcher(x.device).logreg_step(x, y, N, d, K, bool(fit_intercept), W, Z, ZD, solver, history, lam, tol, line_steps, state,
+                                          ring, ws)
+
+
+def logreg_softmax(Z):
+    """float64 [N x K] -> (log-probabilities float64 [N x K], labels int32 [N]: the first of the largest entries of every row)"""
+    _need_cuda(Z)
+    if Z.dim() != 2 or not 1 <= Z.shape[0] <= logreg_max_points() or not 2 <= Z.shape[1] <= logreg_max_classes():
+        raise _lib.EvaeError("logreg_softmax: Z must be [N x K] within the caps, got %s" % (tuple(Z.shape),))
+    N, K = Z.shape
+    _dev_tensor("Z", Z, torch.float64, (N, K), "logreg_softmax")
+    logp = torch.empty((N, K), dtype=torch.float64, device=Z.device)
+    labels = torch.empty(N, dtype=torch.int32, device=Z.device)
+    launch.Launcher(Z.device).logreg_softmax(Z, N, K, logp, labels)
+    return logp, labels
+
+
+# ------------------------------------------------------------------------------------------------
 # dense layers
 # ------------------------------------------------------------------------------------------------
 # The launches of this section go through evae/launch.py's Launcher (workspace names, entry points, the probe's names), built

@@ -1250,6 +1250,70 @@ size_t evae_sym_congruence_workspace_bytes(int d);
 int evae_sym_congruence(const double* A /* [d x d] */, const double* S /* [d x d] */, double* out /* [d x d] */, int d, void* ws,
                         size_t ws_bytes, evae_stream_t stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Linear probe of the latent space in fp64: multinomial (softmax) regression with an L2 penalty by L-BFGS (evae/linear.py).
+ * csrc/evae_logreg.hip; DESIGN 3.7i.  Rows are contiguous fp32 [N x d]; every accumulation is fp64 in a fixed order, the only
+ * atomic is an integer ticket, so equal inputs give bit-equal outputs.  2 <= K <= evae_logreg_max_classes() = 256, 1 <= d <=
+ * evae_logreg_max_features() = 256, 1 <= N <= evae_logreg_max_points() = 2^20, 1 <= history <= evae_logreg_max_history() = 64,
+ * 1 <= line_steps <= evae_logreg_max_line_steps() = 32; a shape whose Z and Z_D [N x K] plus workspace exceed
+ * evae_logreg_max_bytes() = 2^30 is refused.  Every buffer is the caller's.
+ *
+ * With a_n = (x_n, 1), p = d + 1 (p = d when fit_intercept == 0), L = K p:
+ *   f(W) = sum_n [ lse_k(a_n . w_k) - a_n . w_{y_n} ] + (lambda / 2) sum_k sum_{c<d} W_kc^2,  W [K x p], the intercept column last.
+ * solver: one fp64 buffer of evae_logreg_solver_doubles(d, K, fit_intercept, history): G [L] | Q [L] | D [L] | S [m x L] |
+ *   Y [m x L] | sy [m] | yy [m] | alpha [m] | scal [8] (pairs held, next slot, max|G| / N, ww, 0 ..).  Q is scratch.
+ * state [8]: iterations, done, converged, f, t, j, line search failed, G.D.
+ * logits: out[n][k] = sum_c x_nc W_kc by fma in ascending c, then + W_kd.  A row's bits depend on the row and on W alone.
+ * line: from Z, Z_D, W, the solver's D, state[3] = f and state[7] = G.D: the losses of the trial logits fma(t_j, Z_D, Z), t_j = 2^-j,
+ *   j < line_steps (row maximum subtracted, exponentials added in class order), per chunk of evae_logreg_chunk_rows() = 1024
+ *   rows, the chunks in chunk order, plus (lambda / 2)(ww + 2 t wd + t^2 dd); the first j with f_j <= f + 1e-4 t_j G.D gives
+ *   state[4] = t, state[5] = j, ring[iterations] = j (ring may be NULL) and W += t D.  No such j: state[6] = state[1] = 1,
+ *   state[5] = -1, W as it was.  A label outside [0, K) is the caller's to refuse; the kernels read nothing through it.
+ * grad: Z += state[4] Z_D (0: Z_D is not read), R = softmax(Z) - onehot(y) INTO Z_D, sum_n R_nk a_nc per chunk in row order and
+ *   the chunk's loss into ws.
+ * finish: one workgroup: G = the chunks in chunk order + lambda W on the penalised columns; when state[4] != 0 the pair (t D,
+ *   G - G_old) enters the history if s.y > 0 and iterations += 1; f; done = converged = (max|G| / N <= tol); else the two-loop
+ *   recursion (scaling s.y / y.y of the newest pair, 1 / max|G| without one) gives D and G.D.
+ * direction: the two-loop recursion alone, from the G and the pairs in the solver.
+ * begin: zeroes state, solver and the ticket, then logits (Z from W), grad, finish: f, G, D at the caller's W (the driver's: 0).
+ * step: logits (Z_D from D), line, grad, finish -- four launches, each returning at once when state[1] != 0.  The workspace
+ *   must be the one begin was given.
+ * softmax: logp[n][k] = z_nk - lse(z_n) and labels[n] = the first k of the largest z_nk; either may be NULL.
+ */
+int evae_logreg_max_classes(void);
+int evae_logreg_max_features(void);
+int evae_logreg_max_points(void);
+int evae_logreg_max_history(void);
+int evae_logreg_max_line_steps(void);
+int evae_logreg_chunk_rows(void);
+size_t evae_logreg_max_bytes(void);
+size_t evae_logreg_solver_doubles(int d, int K, int fit_intercept, int history);
+size_t evae_logreg_workspace_bytes(int N, int d, int K, int fit_intercept, int line_steps);
+int evae_logreg_logits(const float* x /* [N x d] */, int N, int d, const double* W /* [K x p] */, int K, int fit_intercept,
+                       double* out /* [N x K] */, evae_stream_t stream);
+int evae_logreg_line(const double* Z /* [N x K] */, const double* ZD /* [N x K] */, const int* y /* [N] */, int N, int d, int K,
+                     int fit_intercept, double* W /* [K x p] */, double* solver, int history, double lambda, int line_steps,
+                     double* state /* [8] */, int* ring /* [ring_len] or NULL */, int ring_len, void* ws, size_t ws_bytes,
+                     evae_stream_t stream);
+int evae_logreg_grad(const float* x /* [N x d] */, const int* y /* [N] */, int N, int d, int K, int fit_intercept, int line_steps,
+                     double* Z /* [N x K] */, double* ZD /* [N x K] */, const double* state /* [8] */, void* ws, size_t ws_bytes,
+                     evae_stream_t stream);
+int evae_logreg_finish(int N, int d, int K, int fit_intercept, int line_steps, const double* W /* [K x p] */, double* solver,
+                       int history, double lambda, double tol, double* state /* [8] */, void* ws, size_t ws_bytes,
+                       evae_stream_t stream);
+int evae_logreg_direction(double* solver, int d, int K, int fit_intercept, int history, double* state /* [8] */,
+                          evae_stream_t stream);
+int evae_logreg_begin(const float* x /* [N x d] */, const int* y /* [N] */, int N, int d, int K, int fit_intercept,
+                      double* W /* [K x p] */, double* Z /* [N x K] */, double* ZD /* [N x K] */, double* solver, int history,
+                      double lambda, double tol, int line_steps, double* state /* [8] */, void* ws, size_t ws_bytes,
+                      evae_stream_t stream);
+int evae_logreg_step(const float* x /* [N x d] */, const int* y /* [N] */, int N, int d, int K, int fit_intercept,
+                     double* W /* [K x p] */, double* Z /* [N x K] */, double* ZD /* [N x K] */, double* solver, int history,
+                     double lambda, double tol, int line_steps, double* state /* [8] */, int* ring /* [ring_len] or NULL */,
+                     int ring_len, void* ws, size_t ws_bytes, evae_stream_t stream);
+int evae_logreg_softmax(const double* Z /* [N x K] */, int N, int K, double* logp /* [N x K] or NULL */,
+                        int* labels /* [N] or NULL */, evae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
